@@ -23,7 +23,8 @@ Prints ONE JSON line (rank 0).  roofline: the DOMINANT KERNEL -- the radiance-ne
 launch time, measured with HIP events on the launch stream inside the timed region by the library's launch probe
 (include/sahs_nerf.h: sahs_probe_*); frac_executed prices the MACs the kernel actually issues (padded tiles, per-frame
 constants folded away); roofline.chain prices all field launches together against the reference's algorithmic work
-(1,855,744 FLOP per sample evaluation).  At N=1 the line also carries:
+(1,855,744 FLOP per sample evaluation).  A plain run is that headline alone.  With --full, at N=1 (fp32, audio
+model) the line also carries:
   cpu_baseline        the reference's CPU path: the torch-eager restatement (oracle/torch_eager.py, pinned to the reference
                       by tests/test_torch_eager_vs_golden.py) with torch.set_num_threads(all host cores) on the central 64x64
                       crop of the same frame, whose outputs are also checked against the GPU frame (configs[0]-size parity);
@@ -33,6 +34,9 @@ constants folded away); roofline.chain prices all field launches together agains
   nerface_fp32, num_fine128, train_T2048 (backward products in f32), train_T2048_bf16x3 (the default: split-bf16 backward), spade
                       the secondary workloads of SURVEY.md section 8d / 8f.
 Only this file's cpu_baseline / torch_gpu_baseline legs import anything under oracle/ (the thing timed there, never the product path).
+
+--dump-outputs DIR: after the timed steps, the last step's 8-tuple (what run_one_iter_of_nerf returns) as DIR/<name>.npy, float32.
+Inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import importlib
@@ -268,6 +272,26 @@ def rows_of(out):
     """The 8-tuple as (R, 36) rows (SAHS_ROW_* order)."""
     R = out[1].numel()
     return torch.cat([o.reshape(R, -1) for o in out], dim=1)
+
+
+OUT_NAMES = ["rgb_c", "disp_c", "acc_c", "rgb_f", "disp_f", "acc_f", "w_bg", "depth_f"]      # run_one_iter_of_nerf's 8-tuple
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every output array as <path>/<name>.npy in float32 (a W512 frame: 36 floats x 262,144 rays = 37.7 MB).  Above
+    DUMP_BYTES in all, the same fixed, seeded sample of rays is written from every array, each flattened to (rays, -1)."""
+    outs = list(out) if isinstance(out, (tuple, list)) else [out]
+    names = OUT_NAMES if len(outs) == len(OUT_NAMES) else ["out%d" % i for i in range(len(outs))]
+    arrs = [o.detach().float().cpu().numpy() for o in outs]
+    rays = min(a.size for a in arrs)
+    total = sum(a.nbytes for a in arrs)
+    if total > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rays, rays * DUMP_BYTES // total, replace=False))
+        arrs = [a.reshape(rays, -1)[keep] for a in arrs]
+    os.makedirs(path, exist_ok=True)
+    for n, a in zip(names, arrs):
+        np.save(os.path.join(path, n + ".npy"), a)
 
 
 def add_secondary_legs(result, pkg, dev, args):
@@ -667,8 +691,10 @@ def main(argv=None):
                     help="fp32 = configs[1] (exact, headline); bf16 = configs[2] (bf16 MFMA operands, fp32 accumulate)")
     ap.add_argument("--arch", default="audio", choices=["audio", "nerface"], help="audio = AudioFaceModel (the headline); nerface = the "
                     "expression-driven NeRFaceModel of config/expression/person_2.yml (profiling of that leg; fp32 or bf16 = mixed precision)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the torch_gpu_baseline / cpu_baseline legs")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only (no bf16 / NeRFace / num_fine128 / training legs)")
+    ap.add_argument("--full", action="store_true", help="beside the headline (N=1, fp32, audio): the secondary legs and the baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the torch_gpu_baseline / cpu_baseline legs")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the bf16 / NeRFace / num_fine128 / training / spade legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     args = ap.parse_args(argv)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # BEFORE any GPU call: the parent only launches and relays
@@ -716,11 +742,13 @@ def main(argv=None):
         if one_gpu:
             result["collective_backend"] = backend
             result["rehearsal"] = "every rank on cuda:0, %s collectives: the N > 1 code path on one GPU, not a measurement" % backend
-        if args.precision == "fp32" and world == 1 and args.arch == "audio":
-            if not args.no_secondary:
-                add_secondary_legs(result, pkg, dev, args)
-            if not args.no_cpu_baseline:
-                add_baselines(result, out, rend, pkg, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    if args.full and not injected and args.precision == "fp32" and world == 1 and args.arch == "audio":
+        if not args.no_secondary:
+            add_secondary_legs(result, pkg, dev, args)
+        if not args.no_cpu_baseline:
+            add_baselines(result, out, rend, pkg, dev)
     progress("done")
     result["bench_wall_s"] = time.perf_counter() - t_start
     if rank == 0:

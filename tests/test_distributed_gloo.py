@@ -92,6 +92,48 @@ def test_bench_main_self_launch_over_gloo(size):
     assert p.returncode != 0 and len(lines) == 1 and "error" in json.loads(lines[0]) and json.loads(lines[0])["n_gpus"] == 2, p.stdout
 
 
+def test_bench_dump_outputs_over_gloo(tmp_path):
+    """--dump-outputs: rank 0 writes the last timed step's frame as float32 .npy files after the timed steps; the inputs are seeded,
+    so two runs with the same arguments write the same arrays."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(SAHS_BENCH_BACKEND="gloo", SAHS_BENCH_RENDERER=os.path.join(REPO, "tests", "gloo_bench_renderer.py") + ":make", OMP_NUM_THREADS="2")
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "5",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert sorted(os.listdir(d)) == ["out0.npy"]      # the injected renderer's step returns the (R, 36) rows
+        dumps.append(np.load(d / "out0.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (25, 36) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_dump_outputs_samples_large_frames(tmp_path, monkeypatch):
+    """Above the size cap, every array is cut to the same fixed, seeded sample of rays, within the cap in all."""
+    import importlib.util
+    sp = importlib.util.spec_from_file_location("sahs_bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(sp)
+    sp.loader.exec_module(bench)
+    H = W = 16
+    ray = torch.arange(H * W, dtype=torch.float32).reshape(H, W)
+    widths = [15, 1, 1, 15, 1, 1, 1, 1]
+    out = tuple(ray[..., None].expand(H, W, c).clone() if c > 1 else ray.clone() for c in widths)
+    cap = 4 * 36 * 100 + 7
+    monkeypatch.setattr(bench, "DUMP_BYTES", cap)
+    for run in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / run))
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in bench.OUT_NAMES}
+    assert sum(a.nbytes for a in got.values()) <= cap
+    keep = got["disp_c"][:, 0]
+    assert len(keep) == 100 and len(np.unique(keep)) == 100
+    for n, c in zip(bench.OUT_NAMES, widths):
+        assert got[n].dtype == np.float32 and got[n].shape == (100, c)
+        assert np.array_equal(got[n], np.repeat(keep[:, None], c, axis=1))
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy")))
+
+
 def test_bench_main_wall_clock_guard_ends_a_hung_run():
     """A run whose ranks never finish (here: a renderer that sleeps; on hardware: a wedged rendezvous or RCCL collective) is ended by the
     parent's wall-clock guard: the children's process group is terminated, ONE JSON line {"error", "n_gpus"} is printed, the exit status is
