@@ -92,18 +92,28 @@ class EagerField:
         N, C, H, W, D = s.shape
         return s.permute(0, 4, 3, 2, 1).reshape(N * H * W * D, C)
 
-    def forward(self, level, x, audio, pose):
+    def forward(self, level, x, audio, pose, driving=None, pose36=None, taps=None):
+        """Optional hooks for the gradient tests (the default call is the reference's): ``driving`` (the per-frame conditioning vector
+        AudioNet makes of ``audio``, or the expression) and ``pose36`` (the pose encoding) given precomputed instead of computed from
+        ``audio`` / ``pose``, so that they can be autograd leaves; ``taps`` (a dict) receives the deformation nets' outputs "warped" (x')
+        and "amb" (w), the seam of the split evaluation."""
         a = self.a
         P = x.shape[0]
         xyz, dirs = x[..., :3], x[..., 3:6]
-        driving = (self.audionet(audio) if a["audionet"] else audio).repeat(P, 1)      # models.py:517-518 / :368
-        pose36 = self.pose_encoding(pose).repeat(P, 1)                                 # :519-521 / :369-370
+        if driving is None:
+            driving = self.audionet(audio) if a["audionet"] else audio
+        if pose36 is None:
+            pose36 = self.pose_encoding(pose)
+        driving = driving.repeat(P, 1)      # models.py:517-518 / :368
+        pose36 = pose36.repeat(P, 1)        # :519-521 / :369-370
         L = a["L"]
         if a["deform"]:
             initial = torch.cat((positional_encoding(xyz, L), driving, pose36), dim=1)
             warped = xyz + torch.tanh(self.deform("warp_field_mlp", "layers_xyz", "fc_final", 6, 4, initial))     # :304-305
             initial = torch.cat((positional_encoding(xyz, L), driving, pose36), dim=1)                           # PE recomputed, :310
             amb = self.deform("hyper_sheep_mlp", "layers_ambient", "fc_ambient", 6, 4, initial)
+            if taps is not None:
+                taps["warped"], taps["amb"] = warped, amb
             enc = torch.cat((positional_encoding(warped, L), positional_encoding(amb, a["L_amb"], a["amb_inc"])), dim=1)
         else:
             warped = xyz                                                                                          # :316-327

@@ -123,3 +123,54 @@ def test_nerface_forward_and_gradients(weights_mod, arch):
         if "grad_" + k in g.keys():
             close(gr, g["grad_" + k], 5e-3, ra * float(np.abs(g["grad_" + k]).max()) + 1e-9, "grad " + k)
     close(expr.grad, g["grad_expression"], 5e-3, ra * float(np.abs(g["grad_expression"]).max()), "grad expression")
+
+
+@pytest.mark.parametrize("arch", ["audio", "nerface", "nerface_static"])
+def test_field_conditioning_hooks(weights_mod, arch):
+    """EagerField.forward with the conditioning given precomputed (driving=, pose36=) and the seam tapped (taps=), the form the float64
+    gradient tests of the HIP backward use (tests/test_gpu_backward_tails.py), equals the default call bit for bit, forward and float64
+    gradients, at a tiny P; and the tapped seam carries the gradient that reaches the deformation nets."""
+    sd_np = weights_mod.hash_state_dict(0, 8.0, 30.0, model=arch) if arch != "audio" else weights_mod.hash_state_dict(0, 8.0, 30.0)
+    gen = torch.Generator().manual_seed(3)
+    P = 5
+    x = torch.cat([torch.rand(P, 3, generator=gen, dtype=torch.float64) * 0.4 - 0.2, torch.randn(P, 3, generator=gen, dtype=torch.float64)], 1)
+    cond = torch.randn(16, 29, generator=gen, dtype=torch.float64) if arch == "audio" else torch.randn(76, generator=gen, dtype=torch.float64) * 0.5
+    pose = torch.from_numpy(np.concatenate([np.eye(3), [[0.0], [0.0], [0.5]]], 1))
+    d_raw = torch.randn(P, 16, generator=gen, dtype=torch.float64)
+
+    def run(hooked):
+        sd = {k: torch.from_numpy(v.copy()).double().requires_grad_(True) for k, v in sd_np.items()}
+        c = cond.clone().requires_grad_(True)
+        f = TE.EagerField(sd, num_coarse=P, num_fine=0, arch=arch)
+        taps = {}
+        if hooked:
+            drv = f.audionet(c) if arch == "audio" else c
+            raw = f.forward("fine", x, None, None, driving=drv, pose36=f.pose_encoding(pose), taps=taps)
+        else:
+            raw = f.forward("fine", x, c, pose)
+        (raw * d_raw).sum().backward()
+        return raw.detach(), {k: v.grad for k, v in sd.items()}, c.grad, taps
+
+    raw0, g0, c0, _ = run(False)
+    raw1, g1, c1, taps = run(True)
+    assert torch.equal(raw0, raw1)
+    assert g0.keys() == g1.keys()
+    for k in g0:
+        assert (g0[k] is None) == (g1[k] is None), k
+        if g0[k] is not None:
+            assert torch.equal(g0[k], g1[k]), k
+    assert torch.equal(c0, c1)
+    assert ("warped" in taps) == (arch != "nerface_static")
+    if "warped" in taps:
+        assert taps["warped"].shape == (P, 3) and taps["amb"].shape == (P, 2 if arch == "audio" else 1)
+        # the seam: d raw-loss / d (x', w) through the radiance net, pulled back through the deformation nets, is the deformation nets'
+        # whole gradient (they reach the output through x' and w only)
+        sd ={k: torch.from_numpy(v.copy()).double().requires_grad_(True) for k, v in sd_np.items()}
+        f = TE.EagerField(sd, num_coarse=P, num_fine=0, arch=arch)
+        taps = {}
+        drv = f.audionet(cond) if arch == "audio" else cond
+        raw = f.forward("fine", x, None, None, driving=drv, pose36=f.pose_encoding(pose), taps=taps)
+        gw, ga = torch.autograd.grad((raw * d_raw).sum(), [taps["warped"], taps["amb"]], retain_graph=True)
+        k = "warp_field_mlp.fc_final.bias"
+        via_seam = torch.autograd.grad((taps["warped"] * gw).sum(), [sd[k]])[0]
+        assert torch.allclose(via_seam, g0[k], rtol=1e-12, atol=1e-15), k
