@@ -257,19 +257,30 @@ int sahs_route_xw_grad(long N, int Sc, int nf, const int32_t *src, const float *
  * Process-wide; enable < 0 queries; SAHS_BF16_EXACT_LEAKY=1 in the environment selects it at first use.  Returns the state in force. */
 int sahs_bf16_exact_leaky(int enable);
 
-/* The fused backward walk (round 4; SAHS_MODEL_AUDIO; in the arithmetic sahs_backward_gemm_precision names: split-bf16 operands,
+/* The fused backward walk (every model; in the arithmetic sahs_backward_gemm_precision names: split-bf16 operands,
  * SAHS_BF16X3, or exact fp32 products, SAHS_F32 -- the reference's).  Replaces the ~38 GEMM launches sahs_model_field_backward_split makes
  * per part -- autograd of modules.py:254-295 (NeRFMLP), :371-390 (WarpFieldMLP), :444-462 (HyperSheetMLP) as driven by
  * train_stage_rays_auto.py:437-499 -- by two or three: one sample-major data-gradient chain and the weight gradients over job tables.  The (leaky-)ReLU masks come from SIGN BITS the saving forward writes beside the activations:
  * sahs_model_field_forward_split_save_bits = sahs_model_field_forward_split_save that also fills bits_out, N*S*sahs_model_bits_words_part(
  * model, mode) 32-bit words (mode 0: [deformation planes | radiance planes]).  sahs_model_field_backward_fused takes the same arguments as
  * sahs_model_field_backward_split plus bits_in (the planes of `part`; part 3: both, as written by a mode-0 save); workspace:
- * sahs_model_field_backward_fused_workspace_words(model, part, P) floats (-1: not built for the model).  Same results as the per-layer
- * walk up to summation order (tests/test_gpu_training.py). */
+ * sahs_model_field_backward_fused_workspace_words(model, part, P) floats (-1: a part the model does not have).  Same results as the per-layer
+ * walk up to summation order (tests/test_gpu_training.py, tests/test_gpu_nerface_fused.py).
+ * Models and parts: SAHS_MODEL_AUDIO and SAHS_MODEL_NERFACE parts 1 (deformation nets), 2 (radiance nets of `level`), 3 (both);
+ * SAHS_MODEL_NERFACE_STATIC part 3 only (= its radiance nets: no seam gradient, xw_grad_in / xw_grad_out unused), parts 1 and 2 fail
+ * with "this model has no deformation nets".  Sign words per sample (sahs_model_bits_words_part, part 1 / 2 / 0 = 3):
+ * AudioFaceModel 48 / 96 / 144, NeRFaceModel 48 / 64 / 112, NeRFaceModel without deformation -- / 64 / 64.
+ * Workspace: per-sample floats times P plus a constant part (the feature grid twice, the part's transposed weight stream, scratch):
+ *   AudioFaceModel  part 1: 1,256   part 2: 3,736   part 3: 5,000      NeRFaceModel  part 1: 1,288   part 2: 2,808   part 3: 4,104
+ *   NeRFaceModel without deformation  part 3: 2,616
+ * The static model's saving forward is the whole-network one: sahs_model_field_forward_save_bits = sahs_model_field_forward_save that also
+ * fills bits_out, N*S*sahs_model_bits_words_part(model, 0) words (every model; the planes a mode-0 split save writes). */
 long sahs_model_bits_words_part(int model, int part);
 int sahs_model_field_forward_split_save_bits(int model, const void *packed, const float *frame, int level, int mode, long N, int S, const float *rays,
                                              int ray_stride, const float *z, float *raw, float *xw, int xw_row, int xw_col0, const int32_t *src,
                                              float *act_out, uint32_t *bits_out, void *stream);
+int sahs_model_field_forward_save_bits(int model, const void *packed, const float *frame, int level, long N, int S, const float *rays,
+                                       int ray_stride, const float *z, float *raw, float *act_out, uint32_t *bits_out, void *stream);
 /* The same buffers written by the split-operand kernels (field_bf16x3.hip; `packed` = the SAHS_BF16X3 pack of the weights): the training
  * forward at three bf16 MFMAs per product instead of fp32 MFMAs.  Modes 1 (deformation nets) and 2 (radiance nets); the saved values are
  * those kernels' own (within a few 1e-6 relative of the fp32 kernel's), the signs are the signs of the values saved. */

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsahs_nerf.so")
 SOURCES = ["capi.hip", "pack.hip", "render_ops.hip", "spade_ops.hip", "field_f32.hip", "field_bf16w.hip", "field_bf16x3.hip", "field_bwd.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip", "train_bwd.hip"]
 # sources built again for the NeRFaceModel architectures (csrc/sahs_model.hpp: -DSAHS_MODEL=1 / 2, symbols suffixed _nf / _ns)
-MODEL_SOURCES = ["pack.hip", "field_f32.hip", "field_bwd.hip"]
+MODEL_SOURCES = ["pack.hip", "field_f32.hip", "field_bwd.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip"]
 NERFACE_DEFORM_SOURCES = ["field_bf16x3.hip"]      # NeRFaceModel WITH deformation nets (SAHS_MODEL=1): their split-operand kernel (mixed precision)
 MODEL1_SOURCES = ["field_bf16w.hip"]      # NeRFaceModel: the bf16 radiance nets (with deformation nets: those stay fp32; without: the whole net)
 # field kernels: no sNaN-quieting v_max before every fmaxf (activations); NaNs still propagate through the MFMAs
@@ -30,14 +30,20 @@ NO_SCRATCH = {"gemm_dma_kernel": 0, "_ZN4sahs24field_forward_f32_kernelILb0E": 0
               "field_radiance_bf16x3_kernel": 0, "field_deform_bf16x3_kernel": 0, "gemm_tn_split_kernel": 0, "gemm_tn_jobs_kernel": 0,
               "field_backward_chain_rad_kernel": 0, "field_backward_chain_def_kernel": 0, "_ZN4sahs24field_forward_f32_kernelILb1E": 96,
               "gemm_tn_jobs_f32_kernel": 0, "gemm_tn_jobs256_f32_kernel": 0,
-              "field_backward_chain_rad_f32_kernel": 0, "field_backward_chain_def_f32_kernel": 0}
+              "field_backward_chain_rad_f32_kernel": 0, "field_backward_chain_def_f32_kernel": 0,
+              # (the names above match every model's build; the NeRFaceModel instances of the fused walk's chains, spelled out)
+              "_ZN7sahs_nf3bwc31field_backward_chain_rad_kernel": 0, "_ZN7sahs_nf3bwc31field_backward_chain_def_kernel": 0,
+              "_ZN7sahs_ns3bwc31field_backward_chain_rad_kernel": 0, "_ZN7sahs_nf3bwf35field_backward_chain_rad_f32_kernel": 0,
+              "_ZN7sahs_nf3bwf35field_backward_chain_def_f32_kernel": 0, "_ZN7sahs_ns3bwf35field_backward_chain_rad_f32_kernel": 0}
 # Kernels with hand-issued `asm volatile ds_read_b128` + counted waits (csrc/bf16_pipe.hpp): (source, SAHS_MODEL, kernel name pattern).
 # Every build compiles these to ISA as well and runs tools/check_lds_inflight.py on it: an object in which anything touches a read's
 # destination before the wait that retires it is never linked.
 HAND_SCHEDULED = [("field_bf16w.hip", 0, "field_forward_bf16w_kernel"), ("field_bf16w.hip", 1, "field_forward_bf16w_kernel"),
                   ("field_bf16w.hip", 2, "field_forward_bf16w_kernel"), ("field_bf16x3.hip", 0, "field_radiance_bf16x3_kernel"),
                   ("field_bf16x3.hip", 0, "field_deform_bf16x3_kernel"), ("field_bf16x3.hip", 1, "field_deform_bf16x3_kernel"),
-                  ("field_bwd_chain.hip", 0, "field_backward_chain_rad_kernel"), ("field_bwd_chain.hip", 0, "field_backward_chain_def_kernel")]
+                  ("field_bwd_chain.hip", 0, "field_backward_chain_rad_kernel"), ("field_bwd_chain.hip", 0, "field_backward_chain_def_kernel"),
+                  ("field_bwd_chain.hip", 1, "field_backward_chain_rad_kernel"), ("field_bwd_chain.hip", 1, "field_backward_chain_def_kernel"),
+                  ("field_bwd_chain.hip", 2, "field_backward_chain_rad_kernel")]
 # field_bf16w.hip (one wave per SIMD, 512 registers): MFMA accumulators must live in ARCH VGPRs.  Left to its heuristics the compiler
 # puts them in AGPRs, and every accumulator value the activation code touches then costs a v_accvgpr_read -- which, unlike plain VALU
 # work, does NOT hide under the wave's own MFMAs (tools/micro/mfma_valu_overlap.hip: 2 reads per MFMA = 55 cycles per MFMA instead of 36).

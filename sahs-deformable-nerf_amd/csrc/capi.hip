@@ -78,18 +78,17 @@ int sahs_spade_modulate_launch(long planes, long hw, const float *x, const float
     int sahs_field_forward_f32_split_launch##sfx(const float *packed, const float *frame, int level, int mode, long P, int S,      \
                                                  const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,      \
                                                  int xw_row, int xw_col0, const int *src, float *actbuf, int num_cu,                \
-                                                 hipStream_t stream);
+                                                 hipStream_t stream);                                                               \
+    long sahs_field_backward_fused_ws_words##sfx(int part, long P);                                                                 \
+    int sahs_field_backward_fused_launch##sfx(const float *flat, const float *frame, int level, int part, long P, const float *actbuf, \
+                                              const uint32_t *bits, const float *d_raw, const float *xwg_in, float *xwg_out,        \
+                                              float *grad_flat, float *grad_cond, float *ws, int num_cu, hipStream_t stream);
 SAHS_DECLARE_MODEL()
 SAHS_DECLARE_MODEL(_nf)
 SAHS_DECLARE_MODEL(_ns)
 int sahs_bf16w_exact_leaky_state(int set);
 int sahs_bf16w_exact_leaky_state_nf(int set);
 int sahs_bf16w_exact_leaky_state_ns(int set);
-// the fused backward walk (field_bwd.hip + field_bwd_chain.hip): AudioFaceModel only
-long sahs_field_backward_fused_ws_words(int part, long P);
-int sahs_field_backward_fused_launch(const float *flat, const float *frame, int level, int part, long P, const float *actbuf, const uint32_t *bits,
-                                     const float *d_raw, const float *xwg_in, float *xwg_out, float *grad_flat, float *grad_cond, float *ws,
-                                     int num_cu, hipStream_t stream);
 // NeRFaceModel (with deformation) in mixed precision: bf16 radiance nets (field_bf16w.hip built with SAHS_MODEL=1), fp32 deformation nets
 long sahs_layout_packed_words_bf16_nf(void);
 int sahs_pack_weights_bf16_launch_nf(const float *flat, float *packed, hipStream_t stream);
@@ -743,8 +742,35 @@ int sahs_model_field_backward_split(int model, const float *flat_params, const f
 
 long sahs_model_bits_words_part(int model, int part)
 {
-    if (model != SAHS_MODEL_AUDIO || part < 0 || part > 3) return 0;      // only the AudioFaceModel's (fused) backward reads sign bits
-    return sahs_layout_bits_part_words(part == 3 ? 0 : part);
+    if (model < 0 || model > 2 || part < 0 || part > 3) return 0;
+    const int p = part == 3 ? 0 : part;
+    return model == SAHS_MODEL_AUDIO ? sahs_layout_bits_part_words(p) : (model == SAHS_MODEL_NERFACE ? sahs_layout_bits_part_words_nf(p) : sahs_layout_bits_part_words_ns(p));
+}
+
+static int split_bits_launch(int model, const float *packed, const float *frame, int level, int mode, long P, int S, const float *rays, int ray_stride,
+                             const float *z, float *raw, float *xw, int xw_row, int xw_col0, const int32_t *src, float *base, uint32_t *bits, hipStream_t st)
+{
+    auto f = model == SAHS_MODEL_AUDIO ? sahs_field_forward_f32_split_bits_launch
+                                       : (model == SAHS_MODEL_NERFACE ? sahs_field_forward_f32_split_bits_launch_nf : sahs_field_forward_f32_split_bits_launch_ns);
+    return f(packed, frame, level, mode, P, S, rays, ray_stride, z, raw, xw, xw_row, xw_col0, src, base, bits, num_cus(), st);
+}
+
+// the whole-network training forward (sahs_model_field_forward_save) that also writes the sign-bit planes: the saving forward of the
+// NeRFaceModel without deformation nets, whose training does not go through the split evaluation
+int sahs_model_field_forward_save_bits(int model, const void *packed, const float *frame, int level, long N, int S, const float *rays, int ray_stride,
+                                       const float *z, float *raw, float *act_out, uint32_t *bits_out, void *stream)
+{
+    const char *who = "sahs_model_field_forward_save_bits";
+    REQUIRE_MODEL(model, who);
+    REQUIRE(packed && frame && rays && z && raw && act_out && bits_out, who);
+    REQUIRE((level == 0 || level == 1) && N >= 0 && S >= 1 && ray_stride >= 8, "sahs_model_field_forward_save_bits(shape)");
+    REQUIRE(ALIGNED16(packed) && ALIGNED16(frame) && ALIGNED16(raw) && ALIGNED16(act_out) && ALIGNED16(bits_out), "sahs_model_field_forward_save_bits(alignment)");
+    const long P = N * S;
+    REQUIRE(P <= 4000000L, "sahs_model_field_forward_save_bits(at most 4e6 samples per call)");
+    if (P == 0) return 0;
+    int e = split_bits_launch(model, (const float *)packed, frame, level, 0, P, S, rays, ray_stride, z, raw, nullptr, 0, 0, nullptr, act_out, bits_out,
+                              (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
 }
 
 int sahs_model_field_forward_split_save_bits(int model, const void *packed, const float *frame, int level, int mode, long N, int S, const float *rays,
@@ -752,7 +778,8 @@ int sahs_model_field_forward_split_save_bits(int model, const void *packed, cons
                                              float *act_out, uint32_t *bits_out, void *stream)
 {
     const char *who = "sahs_model_field_forward_split_save_bits";
-    REQUIRE(model == SAHS_MODEL_AUDIO, "sahs_model_field_forward_split_save_bits(AudioFaceModel only)");
+    REQUIRE_MODEL(model, who);
+    if (model == SAHS_MODEL_NERFACE_STATIC) return fail(4, "%s: this model has no deformation nets (its saving forward: sahs_model_field_forward_save_bits)%ld", who, 0L);
     if (N == 0) return 0;
     REQUIRE(packed && frame && rays && xw && act_out && bits_out && (level == 0 || level == 1) && N >= 0 && S >= 1 && ray_stride >= 8 && mode >= 0 && mode <= 2, who);
     REQUIRE((mode == 1 || raw) && (mode == 2 || z) && (mode != 2 || src), "sahs_model_field_forward_split_save_bits(buffers of the mode)");
@@ -761,8 +788,8 @@ int sahs_model_field_forward_split_save_bits(int model, const void *packed, cons
     const long P = N * S;
     REQUIRE(P <= 4000000L, "sahs_model_field_forward_split_save_bits(at most 4e6 samples per call)");
     float *base = act_out - act_col0(model, mode) * P;
-    int e = sahs_field_forward_f32_split_bits_launch((const float *)packed, frame, level, mode, P, S, rays, ray_stride, z, raw, xw, xw_row, xw_col0, src, base,
-                                                     bits_out, num_cus(), (hipStream_t)stream);
+    int e = split_bits_launch(model, (const float *)packed, frame, level, mode, P, S, rays, ray_stride, z, raw, xw, xw_row, xw_col0, src, base, bits_out,
+                              (hipStream_t)stream);
     return e ? hip_fail(who, e) : 0;
 }
 
@@ -795,8 +822,9 @@ int sahs_model_field_forward_split_save_bits_x3(int model, const void *packed, c
 
 long sahs_model_field_backward_fused_workspace_words(int model, int part, long P)
 {
-    if (model != SAHS_MODEL_AUDIO || part < 1 || part > 3 || P < 0) return -1;
-    return sahs_field_backward_fused_ws_words(part, P);
+    if (model < 0 || model > 2 || part < 1 || part > 3 || P < 0) return -1;
+    return model == SAHS_MODEL_AUDIO ? sahs_field_backward_fused_ws_words(part, P)
+           : (model == SAHS_MODEL_NERFACE ? sahs_field_backward_fused_ws_words_nf(part, P) : sahs_field_backward_fused_ws_words_ns(part, P));
 }
 
 int sahs_model_field_backward_fused(int model, const float *flat_params, const float *frame, int level, int part, long P, const float *act_in,
@@ -804,7 +832,8 @@ int sahs_model_field_backward_fused(int model, const float *flat_params, const f
                                     float *grad_cond, float *workspace, void *stream)
 {
     const char *who = "sahs_model_field_backward_fused";
-    REQUIRE(model == SAHS_MODEL_AUDIO, "sahs_model_field_backward_fused(AudioFaceModel only)");
+    REQUIRE_MODEL(model, who);
+    if (model == SAHS_MODEL_NERFACE_STATIC && part != 3) return fail(4, "%s: this model has no deformation nets%ld", who, 0L);
     REQUIRE(flat_params && frame && act_in && bits_in && grad_flat && grad_cond && workspace && part >= 1 && part <= 3, who);
     REQUIRE((level == 0 || level == 1) && P >= 0 && P <= 4000000L, "sahs_model_field_backward_fused(0 <= P <= 4e6 samples per call)");
     REQUIRE(((part & 2) ? d_raw != nullptr : xw_grad_in != nullptr) && (part != 2 || xw_grad_out != nullptr),
@@ -813,8 +842,9 @@ int sahs_model_field_backward_fused(int model, const float *flat_params, const f
             (!xw_grad_out || ALIGNED16(xw_grad_out)), "sahs_model_field_backward_fused(alignment)");
     if (P == 0) return 0;
     const float *base = act_in - act_col0(model, part) * P;
-    int e = sahs_field_backward_fused_launch(flat_params, frame, level, part, P, base, bits_in, d_raw, xw_grad_in, xw_grad_out, grad_flat, grad_cond,
-                                             workspace, num_cus(), (hipStream_t)stream);
+    auto f = model == SAHS_MODEL_AUDIO ? sahs_field_backward_fused_launch
+                                       : (model == SAHS_MODEL_NERFACE ? sahs_field_backward_fused_launch_nf : sahs_field_backward_fused_launch_ns);
+    int e = f(flat_params, frame, level, part, P, base, bits_in, d_raw, xw_grad_in, xw_grad_out, grad_flat, grad_cond, workspace, num_cus(), (hipStream_t)stream);
     return e ? hip_fail(who, e) : 0;
 }
 

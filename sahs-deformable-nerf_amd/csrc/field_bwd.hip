@@ -2074,9 +2074,8 @@ extern "C" int SAHS_SYM(sahs_field_backward_split_launch)(const float *flat, con
     return walk();
 }
 
-#if SAHS_MODEL == 0
 // ================================================================================================================================
-// The fused walk (round 4; AudioFaceModel, split-operand arithmetic): per part of the field TWO GEMM-class launches instead of ~38 --
+// The fused walk (round 4: AudioFaceModel; NeRFaceModels since): per part of the field TWO GEMM-class launches instead of ~38 --
 //   1. field_backward_chain_{rad,def}_kernel (field_bwd_chain.hip): the whole data-gradient chain, sample-major, every layer's dZ stored once
 //      into its plane of `dact` (the act:: layout), masks from the sign bits the saving forward wrote;
 //   2. gemm_tn_jobs_kernel: every layer's dW (+ db) = dZ^T X from those planes and the saved activations, one job table;
@@ -2084,28 +2083,30 @@ extern "C" int SAHS_SYM(sahs_field_backward_split_launch)(const float *flat, con
 // part 1: deformation nets (seam gradient xwg_in (P,8) -> parameters); part 2: radiance nets of `level` (d_raw (P,16) -> parameters, seam
 // gradient to xwg_out); part 3: part 2, then part 1 on (its seam gradient + xwg_in).  actbuf / bits: the buffers the saving forward of that
 // part wrote (a plane of column c at actbuf + c * P; for part 3 bits = [deformation planes | radiance planes]).
+// The NeRFaceModel without deformation nets (SAHS_MODEL 2) has part 3 only, which is its radiance part: no deformation chain, and no seam
+// gradient (nothing upstream of the raw sample point has parameters: its chain stops at dT0, the encodings' backward is not run).
 // ================================================================================================================================
 extern "C" {
-long sahs_bwd_chain_stream_hw(int part);
-int sahs_bwd_chain_pack_launch(const float *flat, void *stream_out, int level, int part, hipStream_t stream);
-int sahs_bwd_chain_rad_launch(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf, float *din_a,
-                              float *din_b, int num_cu, hipStream_t stream);
-int sahs_bwd_chain_def_launch(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact, float *g3,
-                              float *dw4, int num_cu, hipStream_t stream);
+long SAHS_SYM(sahs_bwd_chain_stream_hw)(int part);
+int SAHS_SYM(sahs_bwd_chain_pack_launch)(const float *flat, void *stream_out, int level, int part, hipStream_t stream);
+int SAHS_SYM(sahs_bwd_chain_rad_launch)(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf, float *din_a,
+                                        float *din_b, int num_cu, hipStream_t stream);
+int SAHS_SYM(sahs_bwd_chain_def_launch)(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact, float *g3,
+                                        float *dw4, int num_cu, hipStream_t stream);
 // field_bwd_chain_f32.hip: the same chains in exact fp32 products
-long sahs_bwd_chain_f32_stream_floats(int part);
-int sahs_bwd_chain_f32_pack_launch(const float *flat, float *stream_out, int level, int part, hipStream_t stream);
-int sahs_bwd_chain_f32_rad_launch(const float *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf, float *din_a,
-                                  float *din_b, int num_cu, hipStream_t stream);
-int sahs_bwd_chain_f32_def_launch(const float *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact, float *g3,
-                                  float *dw4, int num_cu, hipStream_t stream);
+long SAHS_SYM(sahs_bwd_chain_f32_stream_floats)(int part);
+int SAHS_SYM(sahs_bwd_chain_f32_pack_launch)(const float *flat, float *stream_out, int level, int part, hipStream_t stream);
+int SAHS_SYM(sahs_bwd_chain_f32_rad_launch)(const float *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf, float *din_a,
+                                            float *din_b, int num_cu, hipStream_t stream);
+int SAHS_SYM(sahs_bwd_chain_f32_def_launch)(const float *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact, float *g3,
+                                            float *dw4, int num_cu, hipStream_t stream);
 }
 
 namespace {
 constexpr long RAD_PLANES = act::STRIDE - act::XW, DEF_PLANES = act::XW;        // floats per sample of the dZ planes of a part
 struct FusedWs {      // workspace of one part, in floats
     // the part's transposed weight stream: split bf16 (hi + lo halfwords) or fp32, whichever the walk's arithmetic is
-    static long stream(int part) { const long a = sahs_bwd_chain_stream_hw(part) / 2, b = sahs_bwd_chain_f32_stream_floats(part); return a > b ? a : b; }
+    static long stream(int part) { const long a = SAHS_SYM(sahs_bwd_chain_stream_hw)(part) / 2, b = SAHS_SYM(sahs_bwd_chain_f32_stream_floats)(part); return a > b ? a : b; }
     static long rad(long P) { return P * (RAD_PLANES + 32 + 2 * DIN_LD + 8) + DB_SCRATCH + 2 * GRID_FLOATS + stream(2) + HEAD_FLOATS; }
     static long def(long P) { return P * (DEF_PLANES + 8) + DB_SCRATCH + stream(1); }
 };
@@ -2248,8 +2249,10 @@ struct TnList {
 };
 }  // namespace
 
-extern "C" long sahs_field_backward_fused_ws_words(int part, long P)
+// floats of workspace of a fused walk of `part` over P samples; -1: a part the model does not have
+extern "C" long SAHS_SYM(sahs_field_backward_fused_ws_words)(int part, long P)
 {
+    if (!USE_DEFORM) return part == 3 ? FusedWs::rad(P) : -1;
     return part == 1 ? FusedWs::def(P) : (part == 2 ? FusedWs::rad(P) : FusedWs::rad(P) + FusedWs::def(P) + P * 8);
 }
 
@@ -2268,10 +2271,10 @@ static int fused_rad(const float *flat, const float *frame, int level, long P, c
     if (hipMemsetAsync(dgrid_cl, 0, sizeof(float) * GRID_FLOATS, stream) != hipSuccess) return (int)hipGetLastError();
     if (hipMemsetAsync(heads, 0, sizeof(float) * HEAD_FLOATS, stream) != hipSuccess) return (int)hipGetLastError();
     const bool f32 = !Bwd::x3();      // exact fp32 products (ops.backward_gemm_precision("fp32")): the fp32 chain and job kernels
-    int e = f32 ? sahs_bwd_chain_f32_pack_launch(flat, bstream, level, 2, stream) : sahs_bwd_chain_pack_launch(flat, bstream, level, 2, stream);
+    int e = f32 ? SAHS_SYM(sahs_bwd_chain_f32_pack_launch)(flat, bstream, level, 2, stream) : SAHS_SYM(sahs_bwd_chain_pack_launch)(flat, bstream, level, 2, stream);
     if (e) return e;
-    e = f32 ? sahs_bwd_chain_f32_rad_launch(bstream, P, d_raw, bits, dact, dgridf, din_a, din_b, num_cu, stream)
-            : sahs_bwd_chain_rad_launch(bstream, P, d_raw, bits, dact, dgridf, din_a, din_b, num_cu, stream);
+    e = f32 ? SAHS_SYM(sahs_bwd_chain_f32_rad_launch)(bstream, P, d_raw, bits, dact, dgridf, din_a, din_b, num_cu, stream)
+            : SAHS_SYM(sahs_bwd_chain_rad_launch)(bstream, P, d_raw, bits, dact, dgridf, din_a, din_b, num_cu, stream);
     if (e) return e;
     // ---- encodings + feature grid -> the seam gradient (what the deformation part waits for) ----
     {
@@ -2280,7 +2283,7 @@ static int fused_rad(const float *flat, const float *frame, int level, long P, c
         const long gb = (P + 127) / 128;
         grid_backward_kernel<<<(unsigned)(gb < 8192 ? gb : 8192), 256, 0, stream>>>(P, actbuf, dgridf, grid_cl, dgrid_cl, dxw); b.check();
         grid_transpose_kernel<<<tb, 256, 0, stream>>>(dgrid_cl, grad_flat + F.grid, 1); b.check();
-        encode_backward_kernel<<<2048, 256, 0, stream>>>(P, actbuf, din_a, din_b, dxw, dw, xwg_out); b.check();
+        if (USE_DEFORM) { encode_backward_kernel<<<2048, 256, 0, stream>>>(P, actbuf, din_a, din_b, dxw, dw, xwg_out); b.check(); }
     }
     // ---- every weight gradient of the part: one job table ----
     const float *A = actbuf;
@@ -2344,6 +2347,7 @@ static int fused_rad(const float *flat, const float *frame, int level, long P, c
     return b.err;
 }
 
+#if SAHS_MODEL != 2
 static int fused_def(const float *flat, const float *frame, long P, const float *actbuf, const uint32_t *bits, const float *xwg, float *grad_flat,
                      float *grad_cond, float *ws, int num_cu, hipStream_t stream)
 {
@@ -2353,10 +2357,10 @@ static int fused_def(const float *flat, const float *frame, long P, const float 
     b.zero = db + DB_SCRATCH - 64;
     if (hipMemsetAsync(db, 0, sizeof(float) * DB_SCRATCH, stream) != hipSuccess) return (int)hipGetLastError();
     const bool f32 = !Bwd::x3();
-    int e = f32 ? sahs_bwd_chain_f32_pack_launch(flat, bstream, 0, 1, stream) : sahs_bwd_chain_pack_launch(flat, bstream, 0, 1, stream);
+    int e = f32 ? SAHS_SYM(sahs_bwd_chain_f32_pack_launch)(flat, bstream, 0, 1, stream) : SAHS_SYM(sahs_bwd_chain_pack_launch)(flat, bstream, 0, 1, stream);
     if (e) return e;
-    e = f32 ? sahs_bwd_chain_f32_def_launch(bstream, P, xwg, actbuf, bits, dact, g3, dw4, num_cu, stream)
-            : sahs_bwd_chain_def_launch(bstream, P, xwg, actbuf, bits, dact, g3, dw4, num_cu, stream);
+    e = f32 ? SAHS_SYM(sahs_bwd_chain_f32_def_launch)(bstream, P, xwg, actbuf, bits, dact, g3, dw4, num_cu, stream)
+            : SAHS_SYM(sahs_bwd_chain_def_launch)(bstream, P, xwg, actbuf, bits, dact, g3, dw4, num_cu, stream);
     if (e) return e;
     auto AC = [&](int c) { return actbuf + (long)c * P; };
     auto DA = [&](int c) { return dact + (long)c * P; };
@@ -2401,12 +2405,19 @@ static int fused_def(const float *flat, const float *frame, long P, const float 
     return b.err;
 }
 
-extern "C" int sahs_field_backward_fused_launch(const float *flat, const float *frame, int level, int part, long P, const float *actbuf,
-                                                const uint32_t *bits, const float *d_raw, const float *xwg_in, float *xwg_out, float *grad_flat,
-                                                float *grad_cond, float *ws, int num_cu, hipStream_t stream)
+#endif      // SAHS_MODEL != 2
+
+extern "C" int SAHS_SYM(sahs_field_backward_fused_launch)(const float *flat, const float *frame, int level, int part, long P, const float *actbuf,
+                                                          const uint32_t *bits, const float *d_raw, const float *xwg_in, float *xwg_out, float *grad_flat,
+                                                          float *grad_cond, float *ws, int num_cu, hipStream_t stream)
 {
     if (P <= 0) return 0;
     if (P > 4000000L) return -3;      // 32-bit byte offsets inside a plane (256 floats per sample)
+#if SAHS_MODEL == 2
+    (void)xwg_in; (void)xwg_out;
+    if (part != 3) return -2;         // no deformation nets: nothing to split
+    return fused_rad(flat, frame, level, P, actbuf, bits, d_raw, nullptr, grad_flat, grad_cond, ws, num_cu, stream);
+#else
     if (part == 1) return fused_def(flat, frame, P, actbuf, bits, xwg_in, grad_flat, grad_cond, ws, num_cu, stream);
     if (part == 2) return fused_rad(flat, frame, level, P, actbuf, bits, d_raw, xwg_out, grad_flat, grad_cond, ws, num_cu, stream);
     if (part != 3) return -2;
@@ -2419,5 +2430,5 @@ extern "C" int sahs_field_backward_fused_launch(const float *flat, const float *
         if ((e = (int)hipGetLastError())) return e;
     }
     return fused_def(flat, frame, P, actbuf, bits, seam, grad_flat, grad_cond, ws_def, num_cu, stream);
+#endif
 }
-#endif      // SAHS_MODEL == 0

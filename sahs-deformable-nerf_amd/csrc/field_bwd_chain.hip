@@ -11,17 +11,15 @@
 //   * every dZ tile stored once, fp32, into the plane of its layer (the act:: layout: dZ of a layer sits where its activation sits in
 //     the saved-activation buffer) -- the operands of the weight-gradient launch that follows (field_bwd.hip: gemm_tn_jobs_kernel).
 // Same arithmetic as the per-layer split-operand GEMMs it replaces (hi*hi + hi*lo + lo*hi, fp32 accumulation), a different summation
-// order.  AudioFaceModel only (SAHS_MODEL 0); the other models and SAHS_BWD_GEMM=f32 keep the per-layer walk.
+// order.  Built once per model (sahs_model.hpp): the layer programs below follow each model's trunk (8 layers for the AudioFaceModel, 4 for
+// the NeRFaceModels, skip layer 3 in all) and the NeRFaceModel without deformation nets (SAHS_MODEL 2) has no deformation chain and no
+// encodings' gradient -- nothing upstream of its raw sample point has parameters.
 #include <hip/hip_runtime.h>
 #include <utility>
 #include "sahs_common.hpp"
 #include "sahs_layout.hpp"
 #include "bf16_pipe.hpp"
 #include "bf16x3_pipe.hpp"
-
-#if SAHS_MODEL != 0
-#error "field_bwd_chain.hip is built for the AudioFaceModel only"
-#endif
 
 namespace SAHS_NS {
 namespace bwc {
@@ -41,8 +39,17 @@ struct LayerB {
     long stream_off;      // halfwords, in this part's stream
     int chunk_hw;
 };
+// (the trunk from fc_feat back: T<i>IN = the encodings' rows of a layer that reads [PE(x') | PE(w)], T<i> = its hidden rows)
+#if SAHS_MODEL == 0
 enum RadLayer { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATIN, R_FEAT, R_T7, R_T6, R_T5, R_T4, R_T3IN, R_T3, R_T2, R_T1, R_T0IN, R_COUNT };
+#elif SAHS_MODEL == 1
+enum RadLayer { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATIN, R_FEAT, R_T3IN, R_T3, R_T2, R_T1, R_T0IN, R_COUNT };
+#else
+enum RadLayer { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATIN, R_FEAT, R_T3, R_T2, R_T1, R_COUNT };
+#endif
 enum DefLayer { D_HF, D_H5, D_H4, D_H3, D_H2, D_H1, D_WF, D_W5, D_W4, D_W3, D_W2, D_W1, D_COUNT };
+constexpr int DIN_W = 16 * (KB_XYZ + KB_AMB);      // a row of the encodings' gradient (din_a, din_b): 96 | 128 floats (SAHS_MODEL 0 | 1)
+static_assert(!USE_DEFORM || DIN_W == 96 || DIN_W == 128, "the encodings' rows are one 32-row tile short of or exactly the layer's 4 tiles");
 template <int N> struct ProgB { LayerB layer[N]; long stream_hw; };
 
 constexpr LayerB mkb(int NT32, SegB s0, RowB r0, SegB s1 = {{0, 0}, 0, 0, 0, 0}, SegB s2 = {{0, 0}, 0, 0, 0, 0}, RowB r1 = {0, 0, 0})
@@ -88,17 +95,24 @@ constexpr ProgB<R_COUNT> make_rad()
                       SegB{{c.alpha_w, n.alpha_w}, TR_H, 15, 1, 1});
     // trunk (modules.py:267-274), skip layer 3: [h | PE(x') | PE(w) | pose]
     L[R_FEAT] = mkb(8, sq(c.feat_w, n.feat_w, TR_H, TR_H), RowB{TR_H, 0, TR_H});
+#if SAHS_MODEL == 0
     for (int i = 7; i >= 4; --i) L[R_T7 + (7 - i)] = mkb(8, sq(c.xyz_w[i], n.xyz_w[i], TR_H, TR_H), RowB{TR_H, 0, TR_H});
+#endif
+#if SAHS_MODEL != 2
     L[R_T3IN] = mkb(4, sq(c.xyz_w[3], n.xyz_w[3], TR_H + D_TR_IN, TR_H), RowB{16 * KB_XYZ, TR_H, D_XYZ}, SegB{{0, 0}, 0, 0, 0, 0}, SegB{{0, 0}, 0, 0, 0, 0},
-                    RowB{16 * KB_AMB, TR_H + D_XYZ, D_AMB});                                                      // d [PE(x') | PE(w)] (tile 3: padding)
+                    RowB{16 * KB_AMB, TR_H + D_XYZ, D_AMB});                                                      // d [PE(x') | PE(w)] (audio: tile 3 is padding)
+#endif
     L[R_T3] = mkb(8, sq(c.xyz_w[3], n.xyz_w[3], TR_H + D_TR_IN, TR_H), RowB{TR_H, 0, TR_H});
     L[R_T2] = mkb(8, sq(c.xyz_w[2], n.xyz_w[2], TR_H, TR_H), RowB{TR_H, 0, TR_H});
     L[R_T1] = mkb(8, sq(c.xyz_w[1], n.xyz_w[1], TR_H, TR_H), RowB{TR_H, 0, TR_H});
+#if SAHS_MODEL != 2
     L[R_T0IN] = mkb(4, sq(c.xyz_w[0], n.xyz_w[0], D_TR_IN, TR_H), RowB{16 * KB_XYZ, 0, D_XYZ}, SegB{{0, 0}, 0, 0, 0, 0}, SegB{{0, 0}, 0, 0, 0, 0},
                     RowB{16 * KB_AMB, D_XYZ, D_AMB});
+#endif
     finish(P);
     return P;
 }
+#if SAHS_MODEL != 2
 constexpr ProgB<D_COUNT> make_def()
 {
     ProgB<D_COUNT> P{};
@@ -122,11 +136,15 @@ constexpr ProgB<D_COUNT> make_def()
     finish(P);
     return P;
 }
-constexpr ProgB<R_COUNT> kRad = make_rad();
 constexpr ProgB<D_COUNT> kDef = make_def();
-__device__ const ProgB<R_COUNT> dRad = make_rad();
 __device__ const ProgB<D_COUNT> dDef = make_def();
-constexpr long RAD_HW = kRad.stream_hw, DEF_HW = kDef.stream_hw;      // halfwords of a level's radiance stream / of the deformation stream
+constexpr long DEF_HW = kDef.stream_hw;      // halfwords of the deformation stream
+#else
+constexpr long DEF_HW = 0;                   // (no deformation nets)
+#endif
+constexpr ProgB<R_COUNT> kRad = make_rad();
+__device__ const ProgB<R_COUNT> dRad = make_rad();
+constexpr long RAD_HW = kRad.stream_hw;      // halfwords of a level's radiance stream
 static_assert(RAD_HW % 8 == 0 && DEF_HW % 8 == 0, "16-byte granules");
 
 // ---- transposed, split stream of one part: [layer][tile32][k-step][hi 64 x 8 | lo 64 x 8]; lane 32 h + i of k-step (block b, step st)
@@ -181,8 +199,11 @@ __global__ void __launch_bounds__(256) pack_bwd_stream_kernel(const float *__res
 {
     const long total = (part == 1 ? DEF_HW : RAD_HW) / 16;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+#if SAHS_MODEL != 2
         if (part == 1) pack_one(dDef, flat, out, 0, e);
-        else pack_one(dRad, flat, out, level, e);
+        else
+#endif
+            pack_one(dRad, flat, out, level, e);
     }
 }
 
@@ -428,6 +449,7 @@ field_backward_chain_rad_kernel(const unsigned short *__restrict__ stream, long 
         {   // d feat (no activation behind it), then the trunk
             BwdEp<false, 8, 256> ef;
             ef.slope = 1.0f; ef.base = dact + (long)act::FEAT * Pq; ef.sc = sc;
+#if SAHS_MODEL == 0
             auto e7 = ep256(sbits::BR_T + 8 * 7, act::T + 7 * 256);
             dense_x<4, 4, 1, 8, CHR(R_FEAT), true, 3>(cx, st, dS0, dC0, draw, F, 0, ef, es0);
             auto e6 = ep256(sbits::BR_T + 8 * 6, act::T + 6 * 256);
@@ -457,10 +479,51 @@ field_backward_chain_rad_kernel(const unsigned short *__restrict__ stream, long 
                 Blk dummy[4];
                 dense_x<8, 0, 0, 4, CHR(R_RGBH), true, 7>(cx, st, F, nullptr, nullptr, dummy, 0, eb, e0);
             }
+#elif SAHS_MODEL == 1
+            // 4-layer trunk, skip layer 3 = the last: d feat -> dT3 (-> d [PE(x') | PE(w)], 128 rows = four whole tiles) -> dT2 -> dT1 -> dT0
+            auto e3 = ep256(sbits::BR_T + 8 * 3, act::T + 3 * 256);
+            dense_x<4, 4, 1, 8, CHR(R_FEAT), true, 3>(cx, st, dS0, dC0, draw, F, 0, ef, es0);
+            dense_x<8, 0, 0, 8, CHR(R_T3IN), true, 7>(cx, st, F, nullptr, nullptr, G, 0, e3, ef);      // G = dT3 (last tile pending)
+            BwdEp<false, DIN_W / 32, DIN_W> ea;
+            ea.slope = 1.0f; ea.base = din_a; ea.sc = sc;
+            {
+                Blk dummy[4];
+                dense_x<8, 0, 0, 4, CHR(R_T3), true, 7>(cx, st, G, nullptr, nullptr, dummy, 0, ea, e3);  // d [PE(x') | PE(w)] through the skip layer
+                flush_x<3>(st, ea);      // (its last tile holds PE(w) rows: stored here, nothing after it converts it)
+            }
+            auto e2 = ep256(sbits::BR_T + 8 * 2, act::T + 2 * 256);
+            auto e1 = ep256(sbits::BR_T + 8 * 1, act::T + 1 * 256);
+            dense_x<8, 0, 0, 8, CHR(R_T2), false>(cx, st, G, nullptr, nullptr, F, 0, e2, NoEp{1.0f});
+            auto e0 = ep256(sbits::BR_T + 0, act::T + 0);
+            dense_x<8, 0, 0, 8, CHR(R_T1), true, 7>(cx, st, F, nullptr, nullptr, G, 0, e1, e2);
+            dense_x<8, 0, 0, 8, CHR(R_T0IN), true, 7>(cx, st, G, nullptr, nullptr, F, 0, e0, e1);      // F = dT0
+            BwdEp<false, DIN_W / 32, DIN_W> eb;
+            eb.slope = 1.0f; eb.base = din_b; eb.sc = sc;
+            {
+                Blk dummy[4];
+                dense_x<8, 0, 0, 4, CHR(R_RGBH), true, 7>(cx, st, F, nullptr, nullptr, dummy, 0, eb, e0);
+                flush_x<3>(st, eb);
+            }
+#else
+            // no deformation nets: nothing upstream of the raw sample point has parameters, so the chain stops at dT0 (the encodings' rows
+            // of layers 0 and 3 only enter the weight gradients)
+            (void)din_a; (void)din_b;
+            auto e3 = ep256(sbits::BR_T + 8 * 3, act::T + 3 * 256);
+            dense_x<4, 4, 1, 8, CHR(R_FEAT), true, 3>(cx, st, dS0, dC0, draw, F, 0, ef, es0);
+            auto e2 = ep256(sbits::BR_T + 8 * 2, act::T + 2 * 256);
+            dense_x<8, 0, 0, 8, CHR(R_T3), true, 7>(cx, st, F, nullptr, nullptr, G, 0, e3, ef);
+            auto e1 = ep256(sbits::BR_T + 8 * 1, act::T + 1 * 256);
+            dense_x<8, 0, 0, 8, CHR(R_T2), true, 7>(cx, st, G, nullptr, nullptr, F, 0, e2, e3);
+            auto e0 = ep256(sbits::BR_T + 0, act::T + 0);
+            dense_x<8, 0, 0, 8, CHR(R_T1), true, 7>(cx, st, F, nullptr, nullptr, G, 0, e1, e2);
+            dense_x<8, 0, 0, 8, CHR(R_RGBH), true, 7>(cx, st, G, nullptr, nullptr, F, 0, e0, e1);      // F = dT0 (last tile pending)
+            flush_x<7>(st, e0);
+#endif
         }
     }
 }
 
+#if SAHS_MODEL != 2
 // Deformation nets, backwards.  xwg (P,8): the seam gradient [dx'0 dx'1 dx'2 . dw0 dw1 . .]; actbuf: the saved activations (DX plane:
 // tanh'); bits: the deformation sign planes (sbits::BD_*); dact: dZ planes WH, HH; g3, dw4 (P,4): the heads' pre-activation gradients
 // [dx' (1 - dx^2) | 0], [dw | 0 0] -- the dY operands of the two final layers' weight-gradient jobs.
@@ -560,6 +623,7 @@ field_backward_chain_def_kernel(const unsigned short *__restrict__ stream, long 
         }
     }
 }
+#endif      // SAHS_MODEL != 2
 
 }  // namespace bwc
 }  // namespace SAHS_NS
@@ -567,12 +631,13 @@ field_backward_chain_def_kernel(const unsigned short *__restrict__ stream, long 
 using namespace SAHS_NS;
 using namespace SAHS_NS::bwc;
 
-// halfwords of the transposed stream of `part` (1 deformation nets, 2 radiance nets of one level)
-extern "C" long sahs_bwd_chain_stream_hw(int part) { return part == 1 ? DEF_HW : RAD_HW; }
+// halfwords of the transposed stream of `part` (1 deformation nets, 2 radiance nets of one level; 0 for a part the model does not have)
+extern "C" long SAHS_SYM(sahs_bwd_chain_stream_hw)(int part) { return part == 1 ? DEF_HW : RAD_HW; }
 
-extern "C" int sahs_bwd_chain_pack_launch(const float *flat, void *stream_out, int level, int part, hipStream_t stream)
+extern "C" int SAHS_SYM(sahs_bwd_chain_pack_launch)(const float *flat, void *stream_out, int level, int part, hipStream_t stream)
 {
     const long total = (part == 1 ? DEF_HW : RAD_HW) / 16;
+    if (total <= 0) return (int)hipErrorInvalidValue;
     pack_bwd_stream_kernel<<<(unsigned)((total + 255) / 256), 256, 0, stream>>>(flat, reinterpret_cast<unsigned short *>(stream_out), level, part);
     return (int)hipGetLastError();
 }
@@ -592,16 +657,18 @@ static int launch_chain(K kernel, long P, int num_cu, hipStream_t stream, A... a
     return (int)hipGetLastError();
 }
 
-extern "C" int sahs_bwd_chain_rad_launch(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf,
+extern "C" int SAHS_SYM(sahs_bwd_chain_rad_launch)(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf,
                                          float *din_a, float *din_b, int num_cu, hipStream_t stream)
 {
     return launch_chain(field_backward_chain_rad_kernel, P, num_cu, stream, reinterpret_cast<const unsigned short *>(bstream), P, d_raw, bits, dact,
                         dgridf, din_a, din_b);
 }
 
-extern "C" int sahs_bwd_chain_def_launch(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact,
+#if SAHS_MODEL != 2
+extern "C" int SAHS_SYM(sahs_bwd_chain_def_launch)(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact,
                                          float *g3, float *dw4, int num_cu, hipStream_t stream)
 {
     return launch_chain(field_backward_chain_def_kernel, P, num_cu, stream, reinterpret_cast<const unsigned short *>(bstream), P, xwg, actbuf, bits,
                         dact, g3, dw4);
 }
+#endif

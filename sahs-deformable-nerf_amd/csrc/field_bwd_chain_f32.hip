@@ -9,15 +9,11 @@
 // the sign bits the saving forward wrote (sahs_layout.hpp: sbits -- the forward's lane (q, j) wrote the very word this lane (q, j) reads),
 // store the dZ tile into the plane of its layer (the operand of the weight-gradient launch, field_bwd.hip: gemm_tn_jobs*_f32_kernel).
 // Same planes, seam buffers and launch order as the split-operand chain; sums in a different order than the per-layer GEMMs it replaces
-// (gemm_dma_kernel<false, false>), same exact products.  AudioFaceModel only (SAHS_MODEL 0).
+// (gemm_dma_kernel<false, false>), same exact products.  Built once per model, with the trunk and the parts of field_bwd_chain.hip's programs.
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
 #include "sahs_layout.hpp"
 #include "f32_pipe.hpp"
-
-#if SAHS_MODEL != 0
-#error "field_bwd_chain_f32.hip is built for the AudioFaceModel only"
-#endif
 
 namespace SAHS_NS {
 namespace bwf {
@@ -35,8 +31,15 @@ struct LayerF {
     long stream_off;      // floats, in this part's stream
     int chunk;            // floats per LDS chunk
 };
+#if SAHS_MODEL == 0
 enum RadF { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATA, R_FEATB, R_FEAT, R_T7, R_T6, R_T5, R_T4, R_T3IN, R_T3, R_T2, R_T1,
             R_T0IN, R_COUNT };
+#elif SAHS_MODEL == 1
+enum RadF { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATA, R_FEATB, R_FEAT, R_T3IN, R_T3, R_T2, R_T1, R_T0IN, R_COUNT };
+#else
+enum RadF { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATA, R_FEATB, R_FEAT, R_T3, R_T2, R_T1, R_COUNT };      // (no encodings' rows: field_bwd_chain.hip)
+#endif
+constexpr int DIN_W = 16 * (KB_XYZ + KB_AMB);      // a row of the encodings' gradient (din_a, din_b): 96 | 128 floats (SAHS_MODEL 0 | 1)
 enum DefF { D_HF, D_H5, D_H4, D_H3, D_H2, D_H1, D_WF, D_W5, D_W4, D_W3, D_W2, D_W1, D_COUNT };
 template <int N> struct ProgF { LayerF layer[N]; long stream_floats; };
 
@@ -81,16 +84,23 @@ constexpr ProgF<R_COUNT> make_rad()
     L[R_FEATB] = mkf(sq(c.seg_w[0], n.seg_w[0], TR_H, BR_H), RowF{TR_H, 0, TR_H}, sq(c.dir_w[0], n.dir_w[0], D_DIR_IN, BR_H));
     // trunk (modules.py:267-274), skip layer 3: [h | PE(x') | PE(w) | pose]
     L[R_FEAT] = mkf(sq(c.feat_w, n.feat_w, TR_H, TR_H), RowF{TR_H, 0, TR_H});
+#if SAHS_MODEL == 0
     for (int i = 7; i >= 4; --i) L[R_T7 + (7 - i)] = mkf(sq(c.xyz_w[i], n.xyz_w[i], TR_H, TR_H), RowF{TR_H, 0, TR_H});
+#endif
+#if SAHS_MODEL != 2
     L[R_T3IN] = mkf(sq(c.xyz_w[3], n.xyz_w[3], TR_H + D_TR_IN, TR_H), RowF{16 * KB_XYZ, TR_H, D_XYZ}, SegF{{0, 0}, 0, 0, 0},
                     RowF{16 * KB_AMB, TR_H + D_XYZ, D_AMB});
+#endif
     L[R_T3] = mkf(sq(c.xyz_w[3], n.xyz_w[3], TR_H + D_TR_IN, TR_H), RowF{TR_H, 0, TR_H});
     L[R_T2] = mkf(sq(c.xyz_w[2], n.xyz_w[2], TR_H, TR_H), RowF{TR_H, 0, TR_H});
     L[R_T1] = mkf(sq(c.xyz_w[1], n.xyz_w[1], TR_H, TR_H), RowF{TR_H, 0, TR_H});
+#if SAHS_MODEL != 2
     L[R_T0IN] = mkf(sq(c.xyz_w[0], n.xyz_w[0], D_TR_IN, TR_H), RowF{16 * KB_XYZ, 0, D_XYZ}, SegF{{0, 0}, 0, 0, 0}, RowF{16 * KB_AMB, D_XYZ, D_AMB});
+#endif
     finish(P);
     return P;
 }
+#if SAHS_MODEL != 2
 constexpr ProgF<D_COUNT> make_def()
 {
     ProgF<D_COUNT> P{};
@@ -106,13 +116,18 @@ constexpr ProgF<D_COUNT> make_def()
     finish(P);
     return P;
 }
-constexpr ProgF<R_COUNT> kRad = make_rad();
 constexpr ProgF<D_COUNT> kDef = make_def();
-__device__ const ProgF<R_COUNT> dRad = make_rad();
 __device__ const ProgF<D_COUNT> dDef = make_def();
-constexpr long RAD_FLOATS = kRad.stream_floats, DEF_FLOATS = kDef.stream_floats;
+constexpr long DEF_FLOATS = kDef.stream_floats;
+static_assert(kDef.layer[D_W1].chunk >= PIECE_FLOATS, "the stream's last chunk is whole DMA pieces");
+#else
+constexpr long DEF_FLOATS = 0;      // (no deformation nets)
+#endif
+constexpr ProgF<R_COUNT> kRad = make_rad();
+__device__ const ProgF<R_COUNT> dRad = make_rad();
+constexpr long RAD_FLOATS = kRad.stream_floats;
 // (a DMA piece is 8 KB: a chunk shorter than that is over-read into what follows it in the stream -- never past the stream's end)
-static_assert(kRad.layer[R_T0IN].chunk >= PIECE_FLOATS && kDef.layer[D_W1].chunk >= PIECE_FLOATS, "the stream's last chunk is whole DMA pieces");
+static_assert(kRad.layer[R_COUNT - 1].chunk >= PIECE_FLOATS, "the stream's last chunk is whole DMA pieces");
 
 // ---- transposed stream of one part: [layer][tile16][k-block][lane 64][4]; lane = 16 q + i holds A[16 t + i][16 b + 4 q + r], r = 0..3 (the
 // A-fragment order of f32_pipe.hpp, as pack.hip writes the forward's) ----------------------------------------------------------------------
@@ -143,7 +158,11 @@ __global__ void __launch_bounds__(256) pack_bwd_stream_f32_kernel(const float *_
 {
     const long total = part == 1 ? DEF_FLOATS : RAD_FLOATS;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x)
+#if SAHS_MODEL != 2
         out[e] = part == 1 ? pack_one(dDef, flat, 0, e) : pack_one(dRad, flat, level, e);
+#else
+        out[e] = pack_one(dRad, flat, level, e);
+#endif
 }
 
 // ---- the backward epilogue ------------------------------------------------------------------------------------------------------------
@@ -169,8 +188,10 @@ struct BwdEpF {
     }
 };
 
-constexpr int RAD_MASK_WORDS = 2 * TR_LAYERS + 8, DEF_MASK_WORDS = 12;      // sign words per lane and sample tile
-static_assert(TR_LAYERS == 8, "slots 16.. of the radiance mask words follow the trunk's 16");
+constexpr int RAD_MASK_WORDS = 2 * TR_LAYERS + 8;                        // sign words per lane and sample tile
+[[maybe_unused]] constexpr int DEF_MASK_WORDS = 12;                       // (the deformation kernel's; no such kernel in SAHS_MODEL 2)
+static_assert(DEF_MASK_WORDS <= RAD_MASK_WORDS, "the deformation kernel's mask words fit the radiance kernel's LDS");
+constexpr int MW_C = 2 * TR_LAYERS, MW_S = MW_C + 4;                       // slots of the colour / seg layers' words, behind the trunk's
 constexpr int CHAIN_LDS_BYTES = 2 * LDS_BUF_FLOATS * 4 + (F32_THREADS / WAVE) * RAD_MASK_WORDS * WAVE * 4;      // the two weight-chunk buffers + the waves' mask words
 
 #define CHR(id) (kRad.layer[id].chunk)
@@ -214,7 +235,7 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
         const uint32_t sb_lane = (uint32_t)(p * 4 + q);
 #define DZ(c, w) (dact + (long)(c) * Pq + p * (long)(w) + 4 * q)
         // This lane's 24 sign words of the tile, fetched ONCE and parked in LDS (word k at mw[64 k]: trunk layer l -> 2 l, 2 l + 1; colour
-        // layer i -> 16 + i; seg layer i -> 20 + i).  Fetched where a layer needs them, each was an ordinary global load whose use the compiler
+        // layer i -> MW_C + i; seg layer i -> MW_S + i).  Fetched where a layer needs them, each was an ordinary global load whose use the compiler
         // guards with vmcnt(0) while LDS-DMA is in flight -- a full drain of the weight prefetch (and of the tile stores) in the middle of a
         // chunk, 16 times per sample tile; from LDS the layers read them on the lgkm counter.
         uint32_t *const mw = reinterpret_cast<uint32_t *>(lds_f + 2 * LDS_BUF_FLOATS) + cx.wave * (RAD_MASK_WORDS * WAVE) + cx.lane;
@@ -227,8 +248,8 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                w[16 + i] = bits[(long)(sbits::BR_C + 4 * i) * Pq + sb_lane];
-                w[20 + i] = bits[(long)(sbits::BR_S + 4 * i) * Pq + sb_lane];
+                w[MW_C + i] = bits[(long)(sbits::BR_C + 4 * i) * Pq + sb_lane];
+                w[MW_S + i] = bits[(long)(sbits::BR_S + 4 * i) * Pq + sb_lane];
             }
 #pragma unroll
             for (int k = 0; k < RAD_MASK_WORDS; ++k) mw[WAVE * k] = w[k];
@@ -252,13 +273,13 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
         f32x4 dC0[8], dS0[8];
         {   // colour branch: d_raw -> dC3 -> dC2 -> dC1 -> dC0 -> d grid features
             f32x4 cA[8], cB[8];
-            auto e3 = ep128(16 + 3, act::C + 384);
+            auto e3 = ep128(MW_C + 3, act::C + 384);
             dense_ep<1, 0, 8, CHR(R_D3)>(cx, draw, nullptr, cA, e3);
-            auto e2 = ep128(16 + 2, act::C + 256);
+            auto e2 = ep128(MW_C + 2, act::C + 256);
             dense_ep<8, 0, 8, CHR(R_D2)>(cx, cA, nullptr, cB, e2);
-            auto e1 = ep128(16 + 1, act::C + 128);
+            auto e1 = ep128(MW_C + 1, act::C + 128);
             dense_ep<8, 0, 8, CHR(R_D1)>(cx, cB, nullptr, cA, e1);
-            auto e0 = ep128(16 + 0, act::C + 0);
+            auto e0 = ep128(MW_C + 0, act::C + 0);
             dense_ep<8, 0, 8, CHR(R_GRIDF)>(cx, cA, nullptr, dC0, e0);
             BwdEpF<false> eg{false, 1.0f, {0u, 0u}, dgridf + p * 32 + 4 * q};
             f32x4 g2[2];
@@ -266,13 +287,13 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
         }
         {   // seg branch: d_raw -> dS3 -> dS2 -> dS1 -> dS0
             f32x4 sA[8], sB[8];
-            auto e3 = ep128(20 + 3, act::S + 384);
+            auto e3 = ep128(MW_S + 3, act::S + 384);
             dense_ep<1, 0, 8, CHR(R_S3)>(cx, draw, nullptr, sA, e3);
-            auto e2 = ep128(20 + 2, act::S + 256);
+            auto e2 = ep128(MW_S + 2, act::S + 256);
             dense_ep<8, 0, 8, CHR(R_S2)>(cx, sA, nullptr, sB, e2);
-            auto e1 = ep128(20 + 1, act::S + 128);
+            auto e1 = ep128(MW_S + 1, act::S + 128);
             dense_ep<8, 0, 8, CHR(R_S1)>(cx, sB, nullptr, sA, e1);
-            auto e0 = ep128(20 + 0, act::S + 0);
+            auto e0 = ep128(MW_S + 0, act::S + 0);
             dense_ep<8, 0, 8, CHR(R_FEATA)>(cx, sA, nullptr, dS0, e0);
         }
         f32x4 F[16], G[16];
@@ -282,6 +303,7 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
             BwdEpF<false> ef{true, 1.0f, {0u, 0u}, DZ(act::FEAT, 256)};
             dense_ep<8, 8, 16, CHR(R_FEAT)>(cx, dS0, dC0, F, ef);
         }
+#if SAHS_MODEL == 0
         {   // trunk: d feat -> dT7 -> ... -> dT3 (-> the encodings through the skip layer) -> dT2 -> dT1 -> dT0 (-> the encodings through layer 0)
             auto e7 = ep256(7, act::T + 7 * 256);
             dense_ep<16, 0, 16, CHR(R_T7)>(cx, F, nullptr, G, e7);
@@ -310,10 +332,50 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
                 dense_ep<16, 0, 6, CHR(R_RGBH)>(cx, F, nullptr, d6, ei);
             }
         }
+#elif SAHS_MODEL == 1
+        {   // 4-layer trunk, skip layer 3 = the last: d feat -> dT3 (-> the encodings through the skip layer) -> dT2 -> dT1 -> dT0 (-> layer 0's)
+            auto e3 = ep256(3, act::T + 3 * 256);
+            dense_ep<16, 0, 16, CHR(R_T3IN)>(cx, F, nullptr, G, e3);
+            {
+                BwdEpF<false> ei{false, 1.0f, {0u, 0u}, din_a + p * DIN_W + 4 * q};
+                f32x4 dn[DIN_W / 16];
+                dense_ep<16, 0, DIN_W / 16, CHR(R_T3)>(cx, G, nullptr, dn, ei);
+            }
+#pragma unroll 1
+            for (int l = 2; l >= 0; --l) {             // layers T3, T2, T1 (next chunks: T2, T1, T0IN, all 32 KB) leave dT2..dT0
+                auto el = ep256(l, act::T + l * 256);
+                dense_ep<16, 0, 16, CHR(R_T2)>(cx, G, nullptr, F, el);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) G[i] = F[i];
+            }
+            static_assert(CHR(R_T2) == CHR(R_T1) && CHR(R_T2) == CHR(R_T0IN), "rolled trunk layers");
+            {
+                BwdEpF<false> ei{false, 1.0f, {0u, 0u}, din_b + p * DIN_W + 4 * q};
+                f32x4 dn[DIN_W / 16];
+                dense_ep<16, 0, DIN_W / 16, CHR(R_RGBH)>(cx, G, nullptr, dn, ei);
+            }
+        }
+#else
+        {   // no deformation nets: the chain stops at dT0 (field_bwd_chain.hip)
+            (void)din_a; (void)din_b;
+#pragma unroll 1
+            for (int l = 3; l >= 1; --l) {             // layers FEAT, T3, T2 (next chunks: T3, T2, T1, all 32 KB) leave dT3..dT1
+                auto el = ep256(l, act::T + l * 256);
+                dense_ep<16, 0, 16, CHR(R_T3)>(cx, F, nullptr, G, el);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) F[i] = G[i];
+            }
+            static_assert(CHR(R_T3) == CHR(R_T2) && CHR(R_T3) == CHR(R_T1), "rolled trunk layers");
+            auto e0 = ep256(0, act::T + 0);
+            dense_ep<16, 0, 16, CHR(R_RGBH)>(cx, F, nullptr, G, e0);
+        }
+#endif
 #undef DZ
     }
 }
-static_assert(16 * (KB_XYZ + KB_AMB) == 96, "the encodings' gradient rows (din_a, din_b) are 96 floats");
+static_assert(SAHS_MODEL != 0 || DIN_W == 96, "the encodings' gradient rows (din_a, din_b) are 96 floats");
+
+#if SAHS_MODEL != 2
 
 // Deformation nets, backwards.  xwg (P,8): the seam gradient [dx'0 dx'1 dx'2 . dw0 dw1 . .]; actbuf: the saved activations (DX plane:
 // tanh'); bits: the deformation sign planes (sbits::BD_*); dact: dZ planes WH, HH; g3, dw4 (P,4): the heads' pre-activation gradients
@@ -401,6 +463,7 @@ field_backward_chain_def_f32_kernel(const float *__restrict__ stream, long P, co
         }
     }
 }
+#endif      // SAHS_MODEL != 2
 
 }  // namespace bwf
 }  // namespace SAHS_NS
@@ -409,11 +472,12 @@ using namespace SAHS_NS;
 using namespace SAHS_NS::bwf;
 
 // floats of the transposed fp32 stream of `part` (1 deformation nets, 2 radiance nets of one level)
-extern "C" long sahs_bwd_chain_f32_stream_floats(int part) { return part == 1 ? DEF_FLOATS : RAD_FLOATS; }
+extern "C" long SAHS_SYM(sahs_bwd_chain_f32_stream_floats)(int part) { return part == 1 ? DEF_FLOATS : RAD_FLOATS; }
 
-extern "C" int sahs_bwd_chain_f32_pack_launch(const float *flat, float *stream_out, int level, int part, hipStream_t stream)
+extern "C" int SAHS_SYM(sahs_bwd_chain_f32_pack_launch)(const float *flat, float *stream_out, int level, int part, hipStream_t stream)
 {
     const long total = part == 1 ? DEF_FLOATS : RAD_FLOATS;
+    if (total <= 0) return (int)hipErrorInvalidValue;
     pack_bwd_stream_f32_kernel<<<(unsigned)((total + 255) / 256), 256, 0, stream>>>(flat, stream_out, level, part);
     return (int)hipGetLastError();
 }
@@ -434,14 +498,16 @@ static int launch_chain_f32(K kernel, long P, int num_cu, hipStream_t stream, A.
     return (int)hipGetLastError();
 }
 
-extern "C" int sahs_bwd_chain_f32_rad_launch(const float *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf,
+extern "C" int SAHS_SYM(sahs_bwd_chain_f32_rad_launch)(const float *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf,
                                              float *din_a, float *din_b, int num_cu, hipStream_t stream)
 {
     return launch_chain_f32(field_backward_chain_rad_f32_kernel, P, num_cu, stream, bstream, P, d_raw, bits, dact, dgridf, din_a, din_b);
 }
 
-extern "C" int sahs_bwd_chain_f32_def_launch(const float *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact,
+#if SAHS_MODEL != 2
+extern "C" int SAHS_SYM(sahs_bwd_chain_f32_def_launch)(const float *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact,
                                              float *g3, float *dw4, int num_cu, hipStream_t stream)
 {
     return launch_chain_f32(field_backward_chain_def_f32_kernel, P, num_cu, stream, bstream, P, xwg, actbuf, bits, dact, g3, dw4);
 }
+#endif

@@ -461,7 +461,10 @@ extern "C" int SAHS_SYM(sahs_field_forward_f32_split_bits_launch)(const float *p
 {
     if (P <= 0) return 0;
 #if SAHS_MODEL == 2
-    return -3;      // no deformation nets in this model
+    // no deformation nets in this model: the whole network only -- with saved activations, the training forward that writes its sign bits
+    // (capi: sahs_model_field_forward_save_bits)
+    if (mode != FIELD_ALL || actbuf == nullptr) return -3;
+    return launch_field<true, FIELD_ALL>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, actbuf, xw, xw_row, xw_col0, nullptr, num_cu, stream, bits);
 #else
     if (actbuf != nullptr) {
         if (mode == FIELD_ALL)

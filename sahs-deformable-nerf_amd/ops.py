@@ -364,14 +364,22 @@ class LaunchProbe:
 # ---------------------------------------------------------------------------------------------------------
 # training path
 # ---------------------------------------------------------------------------------------------------------
-def field_forward_save(packed, frame, level, rays, z, arch="audio"):
+def field_forward_save(packed, frame, level, rays, z, arch="audio", bits=None):
     """fp32 field forward that also returns the saved activations for field_backward: ONE buffer of P * act_words floats laid out
     as a dense [P x width] plane per layer (plane c starts at float c * P; sahs_layout.hpp, namespace act) -- NOT one row per
-    sample, so it can only be handed to field_backward whole, with the same P."""
+    sample, so it can only be handed to field_backward whole, with the same P.  bits (alloc_sign_bits(P, FIELD_ALL, arch, device)):
+    also filled with the sign-bit planes (sahs_model_field_forward_save_bits) -- hand both to field_backward_split(..., 3, bits=bits)."""
     packed, frame, rays, z = _req(packed, "packed"), _req(frame, "frame"), _req(rays, "rays"), _req(z, "z")
     N, S = z.shape
     raw = torch.empty(N, S, 16, dtype=torch.float32, device=z.device)
     act = torch.empty(N * S, _fn("act_words_per_sample", arch)[0](), dtype=torch.float32, device=z.device)
+    if bits is not None:
+        bits = _req(bits, "bits", torch.int32)
+        if tuple(bits.shape) != (N * S, int(_fn("bits_words_part", arch)[0](FIELD_ALL))):
+            raise _lib.SahsError("field_forward_save: bits must come from alloc_sign_bits(N * S, FIELD_ALL, arch, device)")
+        f, name = _fn("field_forward_save_bits", arch)
+        check(f(_p(packed), _p(frame), int(level), N, S, _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(act), _p(bits), _stream()), name)
+        return raw, act
     f, name = _fn("field_forward_save", arch)
     check(f(_p(packed), _p(frame), int(level), N, S, _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(act), _stream()), name)
     return raw, act
@@ -442,9 +450,10 @@ def field_forward_split_save(packed, frame, level, mode, rays, xw, z=None, src=N
 
 def fused_backward(enable=None):
     """The fused backward walk (one data-gradient chain launch + one or two weight-gradient launches per part: include/sahs_nerf.h,
-    sahs_model_field_backward_fused) is taken whenever a backward is given sign bits and the architecture has it (AudioFaceModel), in the
-    arithmetic backward_gemm_precision() names -- split-bf16 operands or exact fp32 products; fused_backward(False) keeps the per-layer walk
-    (the A/B reference).  None queries."""
+    sahs_model_field_backward_fused) is taken whenever a backward is given sign bits -- every architecture has it: the AudioFaceModel and
+    the NeRFaceModel (parts 1, 2, 3), the NeRFaceModel without deformation nets (part 3) -- in the arithmetic backward_gemm_precision()
+    names, split-bf16 operands or exact fp32 products; fused_backward(False) (SAHS_BWD_FUSED=0) keeps the per-layer walk for every
+    architecture (the A/B reference).  None queries."""
     global _FUSED_BACKWARD
     if enable is not None:
         _FUSED_BACKWARD = bool(enable)
@@ -502,7 +511,7 @@ def field_backward_split(flat, frame, level, part, act, grad_flat, grad_cond, d_
     if xw_grad_in is not None and xw_grad_in.numel() != P * 8:
         raise _lib.SahsError("field_backward_split: xw_grad_in must hold (P,8)")
     out = torch.empty(P, 8, dtype=torch.float32, device=act.device) if part == FIELD_RADIANCE else None
-    if bits is not None and _FUSED_BACKWARD and arch == "audio":
+    if bits is not None and _FUSED_BACKWARD:
         bits = _req(bits, "bits", torch.int32)
         bw = lambda m: int(_fn("bits_words_part", arch)[0](int(m)))
         saved_mode = 0 if (full_act or int(part) == 3) else int(part)
@@ -738,15 +747,22 @@ class RenderRaysFn(torch.autograd.Function):
                                     *[t if t is not None else none for t in (bg, noise_c, noise_f)], raw_c, act_c, raw_f, act_r, act_d, src,
                                     *((bits_c, bits_r, bits_d) if bits_c is not None else ())))
         if ctx.kept:     # the same launch chain as sahs_render_rays, with the field activations kept
+            # (the NeRFaceModel without deformation nets trains here: its saves also write the sign bits of its fused walk)
+            N = rays.shape[0]
+            sb = lambda samples: alloc_sign_bits(samples, FIELD_ALL, arch, rays.device) if arch == "nerface_static" else None
             z_c = stratified_depths(rays, num_coarse, lindisp, t_rand)
-            raw_c, act_c = field_forward_save(packed, frame, 0, rays, z_c, arch)
+            bits_c = sb(N * num_coarse)
+            raw_c, act_c = field_forward_save(packed, frame, 0, rays, z_c, arch, bits=bits_c)
             rgb_c, disp_c, acc_c, w_c, _ = composite_forward(raw_c, z_c, rays, noise_c, bg, white_background)
             z_f = resample(z_c, w_c, num_fine, u)
-            raw_f, act_f = field_forward_save(packed, frame, 1, rays, z_f, arch)
+            bits_f = sb(z_f.numel())
+            raw_f, act_f = field_forward_save(packed, frame, 1, rays, z_f, arch, bits=bits_f)
             rgb_f, disp_f, acc_f, w_f, depth_f = composite_forward(raw_f, z_f, rays, noise_f, bg, white_background)
             outs = (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, w_f[:, -1].contiguous(), depth_f)
+            ctx.has_bits = bits_c is not None
             return with_loss(outs, (flat.detach(), audio.detach(), rays, z_c, z_f, frame, packed,
-                                    *[t if t is not None else none for t in (bg, noise_c, noise_f)], raw_c, act_c, raw_f, act_f))
+                                    *[t if t is not None else none for t in (bg, noise_c, noise_f)], raw_c, act_c, raw_f, act_f,
+                                    *((bits_c, bits_f) if bits_c is not None else ())))
         ws = {}
         outs = render_rays(packed, frame, rays, num_coarse, num_fine, precision=SAHS_F32, lindisp=lindisp, white_background=white_background,
                            bg=bg, t_rand=t_rand, noise_c=noise_c, u=u, noise_f=noise_f, workspace=ws, arch=arch)
@@ -765,6 +781,8 @@ class RenderRaysFn(torch.autograd.Function):
         act_d, src = (ctx.saved_tensors[14], ctx.saved_tensors[15]) if ctx.shared else (None, None)
         bits_c, bits_r, bits_d = ctx.saved_tensors[16:19] if (ctx.shared and getattr(ctx, "has_bits", False)) else (None, None, None)
         kept_bits = {0: bits_c, 1: bits_r}
+        if ctx.kept and not ctx.shared and getattr(ctx, "has_bits", False):      # the whole-network saves' sign bits, per level
+            kept_bits = {0: ctx.saved_tensors[14], 1: ctx.saved_tensors[15]}
         xwg_coarse = None      # shared deformation: the fine pass's seam gradient that belongs to the coarse samples
         nc, nf, white, has_bg, has_nc, has_nf = ctx.cfg
         bg = bg if has_bg else None
@@ -779,8 +797,8 @@ class RenderRaysFn(torch.autograd.Function):
         both_levels = loss_ops is not None or (any(g is not None for g in (g_rgb_f, g_disp_f, g_acc_f, g_depth_f, g_wbg)) and
                                                any(g is not None for g in (g_rgb_c, g_disp_c, g_acc_c)))
         # the fused walk is two full-chip persistent launches per part: run side by side they starve each other (measured: 14.0 ms per step on two
-        # streams, 13.3 on one), so the pairwise two-stream issue below is for the per-layer walks only (NeRFaceModels, fused_backward(False))
-        fused_walk = bits_c is not None and _FUSED_BACKWARD and ctx.arch == "audio"
+        # streams, 13.3 on one), so the pairwise two-stream issue below is for the per-layer walks only (fused_backward(False))
+        fused_walk = bits_c is not None and _FUSED_BACKWARD
         if (ctx.shared and nf > 0 and kept is not None and N <= RenderRaysFn.BLOCK_RAYS and both_levels and not fused_walk
                 and not os.environ.get("SAHS_BWD_ONE_STREAM")):
             # The two levels' radiance walks are independent of each other, and so are the two deformation walks that follow them (coarse
@@ -843,6 +861,8 @@ class RenderRaysFn(torch.autograd.Function):
                     else:
                         field_backward_split(flat, frame, 0, 3, act, grad_flat, grad_cond, d_raw=d_raw.view(-1, 16), xw_grad_in=xwg_coarse, arch=ctx.arch,
                                              bits=kept_bits[0])
+                elif kept is not None and kept_bits[level] is not None:      # whole network, sign bits kept: the fused walk (per-layer: fused_backward(False))
+                    field_backward_split(flat, frame, level, 3, act, grad_flat, grad_cond, d_raw=d_raw.view(-1, 16), arch=ctx.arch, bits=kept_bits[level])
                 else:
                     field_backward(flat, frame, level, act, d_raw.view(-1, 16), grad_flat, grad_cond, ctx.arch)
                 del raw, act, d_raw

@@ -1,16 +1,67 @@
 """bench.py's two training legs alone (configs[4]: fp32 backward products, and the default split-bf16 backward), optionally with the
-fused backward walk switched off (--per-layer) for a same-box A/B.  Prints one JSON line."""
+fused backward walk switched off (--per-layer) for a same-box A/B.  --arch nerface / nerface_static: the same two legs for the
+NeRFaceModels (bench.py has none): a 2,048-ray step of config/expression_hotpath.yml -- 64 + 64 samples, noise 0.1, the fused Stage-I
+loss, no optimiser -- with the deformation nets (person_2/3.yml) or without (person_1.yml).  Prints one JSON line."""
 import argparse
 import importlib
 import json
 import os
 import sys
+import time
 
+import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import bench  # noqa: E402
+
+
+def nerface_leg(pkg, dev, arch, rays=2048, steps=5, warmup=2, backward="bf16x3"):
+    """One NeRFaceModel training step as training.train_step takes it (forward + backward through the HIP autograd op, the objective
+    and its gradient inside the HIP launches), timed over `steps` after `warmup`: 2,048 rays x (64 coarse + 128 fine) samples."""
+    W, Tr = pkg.weights, pkg.training
+    cfg = pkg.default_config("expression" if arch == "nerface" else "expression_static")
+    model = pkg.NeRFaceModel(cfg).to(dev).load_flat(W.flatten_state_dict(W.hash_state_dict(0, 8.0, 30.0, model=arch), model=arch)).train()
+    g = torch.Generator(device=dev).manual_seed(3)
+    H = Wd = 128
+    mask = torch.zeros(H, Wd, 12, device=dev)
+    mask.scatter_(2, torch.randint(0, 12, (H, Wd, 1), device=dev, generator=g), 1.0)
+    sel = Tr.sample_training_rays(Tr.semantic_ray_probs(torch.ones(12, device=dev) / 12, mask), rays, g)
+    expr = torch.randn(76, device=dev, generator=g) * 0.5
+    pose = torch.from_numpy(np.concatenate([np.eye(3), [[0.0], [0.0], [0.5]]], 1).astype(np.float32)).to(dev)
+    intr = np.array([1200.0 * H / 512, 1200.0 * H / 512, 0.5, 0.5], np.float32)
+    ro, rd = pkg.get_ray_bundle(H, Wd, intr, pose)
+    ro, rd = ro.reshape(-1, 3)[sel], rd.reshape(-1, 3)[sel]
+    m = mask.reshape(-1, 12)[sel]
+    target = torch.rand(rays, 3, device=dev, generator=g)
+    bg = torch.cat([torch.rand(rays, 3, device=dev, generator=g), torch.ones(rays, 1, device=dev), torch.zeros(rays, 11, device=dev)], 1)
+    cw = Tr.sample_prob_weights(dev)
+
+    def step():
+        outs = pkg.run_one_iter_of_nerf(H, Wd, intr, model, ro, rd, cfg, mode="train", driving=expr, pose=pose, background_prior=bg, inHead=m,
+                                        _loss=(target, m, cw))
+        model.zero_grad(set_to_none=True)
+        outs[8].backward()
+        return outs[8]
+
+    before = pkg.ops.backward_gemm_precision()
+    pkg.ops.backward_gemm_precision(backward)
+    try:
+        for _ in range(warmup):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            loss = step()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / steps
+    finally:
+        pkg.ops.backward_gemm_precision(before)
+    assert bool(torch.isfinite(loss))
+    nc, nf = int(cfg.nerf.train.num_coarse), int(cfg.nerf.train.num_fine)
+    return {"arch": arch, "rays": rays, "samples": [rays * nc, rays * (nc + nf)], "ms_per_step": round(dt * 1e3, 3), "steps": steps,
+            "backward": backward, "fused_backward": pkg.ops.fused_backward()}
 
 
 def main():
@@ -19,12 +70,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--per-layer", action="store_true", help="keep the per-layer backward walk (ops.fused_backward(False))")
     ap.add_argument("--only", default=None, choices=["fp32", "bf16x3", "x3fwd"])
+    ap.add_argument("--arch", default="audio", choices=["audio", "nerface", "nerface_static"])
     a = ap.parse_args()
     pkg = importlib.import_module("sahs-deformable-nerf_amd")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
     pkg.ops.fused_backward(not a.per_layer)
     out = {"fused_backward": pkg.ops.fused_backward()}
+    if a.arch != "audio":      # (the split-operand training forward is the AudioFaceModel's only: no x3fwd leg)
+        if a.only == "x3fwd":
+            ap.error("--only x3fwd is the AudioFaceModel's")
+        for mode in ("fp32", "bf16x3"):
+            if a.only in (None, mode):
+                out["train_%s_T2048%s" % (a.arch, "" if mode == "fp32" else "_bf16x3")] = nerface_leg(pkg, dev, a.arch, steps=a.steps, warmup=a.warmup,
+                                                                                                       backward=mode)
+        print(json.dumps(out))
+        return
     for mode in ("fp32", "bf16x3"):
         if a.only in (None, mode):
             out["train_T2048" + ("" if mode == "fp32" else "_bf16x3")] = bench.train_leg(pkg, dev, steps=a.steps, warmup=a.warmup, backward=mode)
