@@ -27,8 +27,9 @@ extern "C" {
 #define SAHS_ABI_VERSION 1
 #define SAHS_F32 0
 #define SAHS_BF16 1
-#define SAHS_BF16X3 3    /* near-fp32 on the bf16 pipe (AudioFaceModel, split chain only): operands split into bf16 hi + lo, three MFMAs per product,
-                          * fp32 accumulate, in the radiance AND (since round 3) the deformation launches; x' = x + tanh(.) and the encodings stay fp32 arithmetic.
+#define SAHS_BF16X3 3    /* near-fp32 on the bf16 pipe (every model): operands split into bf16 hi + lo, three MFMAs per product, fp32 accumulate,
+                          * in the radiance AND (since round 3) the deformation launches; x' = x + tanh(.) and the encodings stay fp32 arithmetic.
+                          * The models with deformation nets run it as the split chain only; the NeRFaceModel without them as one whole-network launch.
                           * SAHS_X3_DEFORM=f32 in the environment keeps the deformation launches on the fp32 kernel (the round-2 form) */
 /* precision values 2 and 4 are reserved (A/B kernels of development builds, csrc/sahs_common.hpp; not in the shipped library) */
 
@@ -159,10 +160,12 @@ int sahs_conditioning_backward(const float *flat_params, const float *audio, con
  * flat_params is that model's state_dict in order (2,775,633 / 2,311,140 / 2,066,976 values); `driving` is the (16,29) audio
  * window for the AudioFaceModel and the 76-d expression vector (models.py:368 `driving.repeat`) for the NeRFaceModels;
  * rays, depths and outputs are the same, and sahs_get_ray_bundle, sahs_ray_uniforms, sahs_stratified_depths,
- * sahs_composite_forward, sahs_resample, sahs_sample_pdf are model-independent.  Training is SAHS_F32 for every model; rendering
+ * sahs_composite_forward, sahs_resample, sahs_sample_pdf are model-independent.  Training is SAHS_F32 for every model (its saving forward
+ * optionally on the split-operand kernels: sahs_model_field_forward_split_save_bits_x3 / sahs_model_field_forward_save_bits_x3); rendering
  * additionally has SAHS_BF16 for all three (for SAHS_MODEL_NERFACE that means MIXED precision: deformation nets with split bf16 operands --
  * hi + lo, three MFMAs per product, as SAHS_BF16X3 -- + plain-bf16 radiance nets, see sahs_model_field_forward_split) and SAHS_BF16X3 for
- * SAHS_MODEL_AUDIO. */
+ * every model (SAHS_MODEL_AUDIO and SAHS_MODEL_NERFACE: the split chain, packed [hi/lo streams | fp32 pack]; SAHS_MODEL_NERFACE_STATIC:
+ * the whole network, packed as its hi/lo streams alone). */
 #define SAHS_MODEL_AUDIO 0
 #define SAHS_MODEL_NERFACE 1
 #define SAHS_MODEL_NERFACE_STATIC 2
@@ -227,7 +230,10 @@ int sahs_resample_merge(long N, int S, int nf, const float *z, const float *weig
  * SAHS_BF16 for SAHS_MODEL_AUDIO (packed from sahs_pack_weights(..., SAHS_BF16, ...)) and for SAHS_MODEL_NERFACE, where it means MIXED
  * precision: mode 1 runs the deformation nets with split bf16 operands (fp32 kernel under SAHS_X3_DEFORM=f32), mode 2 the bf16 radiance nets
  * (src may then be NULL: sample s of a ray is column s of xw), mode 0 both one after the other (xw_col0 must be 0); packed =
- * sahs_model_pack_weights(SAHS_MODEL_NERFACE, ..., SAHS_BF16, ...) = [bf16 radiance stream | fp32 pack | hi/lo streams].  SAHS_MODEL_NERFACE_STATIC has no deformation nets: its SAHS_BF16 path is sahs_model_field_forward.
+ * sahs_model_pack_weights(SAHS_MODEL_NERFACE, ..., SAHS_BF16, ...) = [bf16 radiance stream | fp32 pack | hi/lo streams].  SAHS_BF16X3 for
+ * SAHS_MODEL_AUDIO and SAHS_MODEL_NERFACE: both modes on the split-operand kernels (mode 0 one after the other, src may be NULL in mode 2),
+ * packed = [hi/lo streams | fp32 pack].  SAHS_MODEL_NERFACE_STATIC has no deformation nets: its SAHS_BF16 and SAHS_BF16X3 paths are
+ * sahs_model_field_forward (the whole network in one launch).
  * PRECONDITION (not checked on the device): every src[ray][s] lies in [0, xw_row) -- it indexes xw's row of that ray (a permutation from
  * sahs_resample_merge satisfies it; ops.field_forward_split validates a caller-made one). */
 int sahs_model_field_forward_split(int model, const void *packed, const float *frame, int precision, int level, int mode, long N, int S, const float *rays,
@@ -282,11 +288,15 @@ int sahs_model_field_forward_split_save_bits(int model, const void *packed, cons
 int sahs_model_field_forward_save_bits(int model, const void *packed, const float *frame, int level, long N, int S, const float *rays,
                                        int ray_stride, const float *z, float *raw, float *act_out, uint32_t *bits_out, void *stream);
 /* The same buffers written by the split-operand kernels (field_bf16x3.hip; `packed` = the SAHS_BF16X3 pack of the weights): the training
- * forward at three bf16 MFMAs per product instead of fp32 MFMAs.  Modes 1 (deformation nets) and 2 (radiance nets); the saved values are
- * those kernels' own (within a few 1e-6 relative of the fp32 kernel's), the signs are the signs of the values saved. */
+ * forward at three bf16 MFMAs per product instead of fp32 MFMAs.  Modes 1 (deformation nets) and 2 (radiance nets) of SAHS_MODEL_AUDIO and
+ * SAHS_MODEL_NERFACE; the saved values are those kernels' own (within a few 1e-6 relative of the fp32 kernel's), the signs are the signs of
+ * the values saved.  sahs_model_field_forward_save_bits_x3: the whole-network form, SAHS_MODEL_NERFACE_STATIC only (the other models fail
+ * with a message that names the split form). */
 int sahs_model_field_forward_split_save_bits_x3(int model, const void *packed, const float *frame, int level, int mode, long N, int S, const float *rays,
                                                 int ray_stride, const float *z, float *raw, float *xw, int xw_row, int xw_col0, const int32_t *src,
                                                 float *act_out, uint32_t *bits_out, void *stream);
+int sahs_model_field_forward_save_bits_x3(int model, const void *packed, const float *frame, int level, long N, int S, const float *rays,
+                                          int ray_stride, const float *z, float *raw, float *act_out, uint32_t *bits_out, void *stream);
 long sahs_model_field_backward_fused_workspace_words(int model, int part, long P);
 int sahs_model_field_backward_fused(int model, const float *flat_params, const float *frame, int level, int part, long P, const float *act_in,
                                     const uint32_t *bits_in, const float *d_raw, const float *xw_grad_in, float *xw_grad_out, float *grad_flat,
@@ -294,8 +304,8 @@ int sahs_model_field_backward_fused(int model, const float *flat_params, const f
 
 /* sahs_model_render_rays writing rows[r * row_ld + column] instead of eight dense arrays (row_ld >= 36; columns 17..33 are
  * left untouched when nf == 0).  Workspace and draws as sahs_render_rays.  Optional extra workspace xw (N,Sc+nf,8) floats, src
- * (N,Sc+nf) int32, z_new (N,nf) floats: when all three are given (nf > 0; any model with deformation nets, SAHS_F32 or SAHS_BF16 -- required for the mixed-precision
- * SAHS_MODEL_NERFACE + SAHS_BF16, which exists as this chain only) the chain evaluates the deformation nets once per
+ * (N,Sc+nf) int32, z_new (N,nf) floats: when all three are given (nf > 0; any model with deformation nets, any precision -- required for the mixed-precision
+ * SAHS_MODEL_NERFACE + SAHS_BF16 and for SAHS_BF16X3 of those models, which exist as this chain only) the chain evaluates the deformation nets once per
  * depth (sahs_model_field_forward_split) -- 6 % less matrix work per frame, identical results. */
 int sahs_model_render_rays_rows(int model, const void *packed, const float *frame, int precision, long N, const float *rays,
                                 int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand,

@@ -100,11 +100,27 @@ long sahs_layout_packed_words_bf16x3(void);
 int sahs_pack_weights_bf16x3_launch(const float *flat, float *packed, hipStream_t stream);
 int sahs_field_deform_bf16x3_launch(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
                                     const float *zvals, float *xw, int xw_row, int xw_col0, int num_cu, hipStream_t stream);
-// NeRFaceModel with deformation nets: the same kernel for its mixed-precision path's deformation launches (field_bf16x3.hip, SAHS_MODEL=1)
+// NeRFaceModel with deformation nets (field_bf16x3.hip, SAHS_MODEL=1): both launches of its SAHS_BF16X3 split chain; the deformation
+// kernel also for its mixed-precision path's deformation launches
 long sahs_layout_packed_words_bf16x3_nf(void);
 int sahs_pack_weights_bf16x3_launch_nf(const float *flat, float *packed, hipStream_t stream);
 int sahs_field_deform_bf16x3_launch_nf(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
                                        const float *zvals, float *xw, int xw_row, int xw_col0, int num_cu, hipStream_t stream);
+int sahs_field_radiance_bf16x3_launch_nf(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
+                                         float *raw, const float *xw, int xw_row, const int *src, int num_cu, hipStream_t stream);
+int sahs_field_deform_bf16x3_save_launch_nf(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
+                                            const float *zvals, float *xw, int xw_row, int xw_col0, float *actbuf, uint32_t *bits, int num_cu,
+                                            hipStream_t stream);
+int sahs_field_radiance_bf16x3_save_launch_nf(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
+                                              float *raw, const float *xw, int xw_row, const int *src, float *actbuf, uint32_t *bits, int num_cu,
+                                              hipStream_t stream);
+// NeRFaceModel without deformation nets (field_bf16x3.hip, SAHS_MODEL=2): the whole network on the split-operand pipe
+long sahs_layout_packed_words_bf16x3_ns(void);
+int sahs_pack_weights_bf16x3_launch_ns(const float *flat, float *packed, hipStream_t stream);
+int sahs_field_forward_bf16x3_launch_ns(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
+                                        const float *zvals, float *raw, int num_cu, hipStream_t stream);
+int sahs_field_forward_bf16x3_save_launch_ns(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
+                                             const float *zvals, float *raw, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream);
 int sahs_field_radiance_bf16x3_launch(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
                                       float *raw, const float *xw, int xw_row, const int *src, int num_cu, hipStream_t stream);
 // ... that also write the saved activations and sign-bit planes of their part (training with the forward on this pipe)
@@ -455,7 +471,7 @@ int sahs_render_rays(const void *packed, const float *frame, int precision, long
 
 // ---- every built architecture behind one family: sahs_model_*(model, ...) ----
 // model: SAHS_MODEL_AUDIO (the functions above), SAHS_MODEL_NERFACE (config/expression/person_2|3.yml),
-// SAHS_MODEL_NERFACE_STATIC (config/expression/person_1.yml: no warp, no hyper sheet).  fp32 forward for the NeRFaceModels.
+// SAHS_MODEL_NERFACE_STATIC (config/expression/person_1.yml: no warp, no hyper sheet).
 struct ModelFns {
     long (*param_count)(void);
     long (*packed_words_f32)(void);
@@ -490,6 +506,9 @@ long sahs_model_packed_words(int model, int precision)
     if (model == SAHS_MODEL_NERFACE && precision == SAHS_BF16)     // mixed precision: [bf16 radiance pack | fp32 pack | hi/lo streams (deformation nets)]
         return nf_mixed_x3_off() + sahs_layout_packed_words_bf16x3_nf();
     if (model == SAHS_MODEL_NERFACE_STATIC && precision == SAHS_BF16) return sahs_layout_packed_words_bf16_ns();
+    if (model == SAHS_MODEL_NERFACE && precision == SAHS_BF16X3)     // the AudioFaceModel's layout: [hi/lo streams | fp32 pack (SAHS_X3_DEFORM=f32)]
+        return sahs_layout_packed_words_bf16x3_nf() + kModels[model].packed_words_f32();
+    if (model == SAHS_MODEL_NERFACE_STATIC && precision == SAHS_BF16X3) return sahs_layout_packed_words_bf16x3_ns();
     return precision == SAHS_F32 ? kModels[model].packed_words_f32() : -1;
 }
 // SAHS_X3_DEFORM=f32 (read once): the split chains' deformation launches run on the fp32 kernel instead of the split-operand one (A/B aid)
@@ -501,12 +520,13 @@ static bool x3_deform_on_f32()
 long sahs_model_executed_macs_part(int model, int precision, int part)
 {
     if (model < 0 || model > 2 || precision < SAHS_F32 || precision > SAHS_BF16X3 || part < 0 || part > 2) return -1;
-    if (precision == SAHS_BF16X3)       // fp32 deformation nets + three bf16 MFMAs per product of the radiance nets
+    if (precision == SAHS_BF16X3)       // three bf16 MFMAs per product, every net
     {
-        if (model != SAHS_MODEL_AUDIO) return -1;
+        if (model == SAHS_MODEL_NERFACE_STATIC) return 3 * sahs_layout_executed_macs_ns(SAHS_BF16, part);      // (no deformation nets: part 1 is 0)
+        auto macs = model == SAHS_MODEL_AUDIO ? sahs_layout_executed_macs : sahs_layout_executed_macs_nf;
         if (x3_deform_on_f32())       // the deformation launches are the fp32 kernel's then: price them as what is issued
-            return (part != 2 ? sahs_layout_executed_macs(SAHS_F32, 1) : 0) + (part != 1 ? 3 * sahs_layout_executed_macs(SAHS_BF16, 2) : 0);
-        return 3 * sahs_layout_executed_macs(SAHS_BF16, part);      // three bf16 MFMAs per product, every net
+            return (part != 2 ? macs(SAHS_F32, 1) : 0) + (part != 1 ? 3 * macs(SAHS_BF16, 2) : 0);
+        return 3 * macs(SAHS_BF16, part);
     }
     if (model == SAHS_MODEL_NERFACE_STATIC && part != 0) return part == 2 ? sahs_layout_executed_macs_ns(precision == SAHS_F32 ? SAHS_F32 : SAHS_BF16, 0) : 0;
     if (model == SAHS_MODEL_NERFACE && precision == SAHS_BF16)      // mixed: split-operand deformation nets (3 MFMAs per product) + bf16 radiance nets
@@ -533,7 +553,16 @@ int sahs_model_pack_weights(int model, const float *flat_params, void *packed, i
         int e = sahs_pack_weights_bf16_launch_ns(flat_params, (float *)packed, (hipStream_t)stream);
         return e ? hip_fail("sahs_model_pack_weights", e) : 0;
     }
-    if (precision != SAHS_F32) return fail(2, "sahs_model_pack_weights: only SAHS_F32 is built for this model %s%ld", "", precision);
+    if (model == SAHS_MODEL_NERFACE && precision == SAHS_BF16X3) {
+        int e = sahs_pack_weights_bf16x3_launch_nf(flat_params, (float *)packed, (hipStream_t)stream);
+        if (!e) e = kModels[model].pack_f32(flat_params, (float *)packed + sahs_layout_packed_words_bf16x3_nf(), (hipStream_t)stream);
+        return e ? hip_fail("sahs_model_pack_weights", e) : 0;
+    }
+    if (model == SAHS_MODEL_NERFACE_STATIC && precision == SAHS_BF16X3) {
+        int e = sahs_pack_weights_bf16x3_launch_ns(flat_params, (float *)packed, (hipStream_t)stream);
+        return e ? hip_fail("sahs_model_pack_weights", e) : 0;
+    }
+    if (precision != SAHS_F32) return fail(2, "sahs_model_pack_weights: precision %s%ld is not built for this model", "", precision);
     int e = kModels[model].pack_f32(flat_params, (float *)packed, (hipStream_t)stream);
     return e ? hip_fail("sahs_model_pack_weights", e) : 0;
 }
@@ -555,9 +584,9 @@ static int field_forward_model(int model, const void *packed, const float *frame
     REQUIRE(packed && frame && rays && z && raw, "sahs_model_field_forward");
     REQUIRE((level == 0 || level == 1) && N >= 0 && S >= 1 && ray_stride >= 8, "sahs_model_field_forward(shape)");
     REQUIRE(ALIGNED16(packed) && ALIGNED16(frame) && ALIGNED16(raw) && (!dbg || ALIGNED16(dbg)), "sahs_model_field_forward(alignment)");
-    if (model == SAHS_MODEL_NERFACE && precision == SAHS_BF16)
-        return fail(2, "sahs_model_field_forward: the mixed-precision NeRFaceModel runs through sahs_model_field_forward_split / "
-                       "sahs_model_render_rays_rows (it needs the xw workspace)%s%ld", "", 0L);
+    if (model == SAHS_MODEL_NERFACE && (precision == SAHS_BF16 || precision == SAHS_BF16X3))
+        return fail(2, "sahs_model_field_forward: the mixed-precision and SAHS_BF16X3 NeRFaceModel run through sahs_model_field_forward_split / "
+                       "sahs_model_render_rays_rows (they need the xw workspace)%s%ld", "", 0L);
     hipStream_t st = (hipStream_t)stream;
     if (model == SAHS_MODEL_NERFACE_STATIC && precision == SAHS_BF16) {
         int e = probed(probe_kind(model, precision, level, 0), N * S, st, [&] {
@@ -565,7 +594,13 @@ static int field_forward_model(int model, const void *packed, const float *frame
         });
         return e ? hip_fail("sahs_model_field_forward", e) : 0;
     }
-    if (precision != SAHS_F32) return fail(2, "sahs_model_field_forward: only SAHS_F32 is built for this model %s%ld", "", precision);
+    if (model == SAHS_MODEL_NERFACE_STATIC && precision == SAHS_BF16X3) {      // the whole network on the split-operand pipe (no debug planes)
+        int e = probed(probe_kind(model, precision, level, 0), N * S, st, [&] {
+            return sahs_field_forward_bf16x3_launch_ns((const float *)packed, frame, level, N * S, S, rays, ray_stride, z, raw, num_cus(), st);
+        });
+        return e ? hip_fail("sahs_model_field_forward", e) : 0;
+    }
+    if (precision != SAHS_F32) return fail(2, "sahs_model_field_forward: precision %s%ld is not built for this model", "", precision);
     int e = probed(probe_kind(model, precision, level, 0), N * S, st, [&] {
         return kModels[model].field_f32((const float *)packed, frame, level, N * S, S, rays, ray_stride, z, raw, dbg, nullptr, num_cus(), st);
     });
@@ -631,39 +666,42 @@ int sahs_model_field_forward_split(int model, const void *packed, const float *f
     if (model == SAHS_MODEL_NERFACE_STATIC) return fail(4, "sahs_model_field_forward_split: this model has no deformation nets%s%ld", "", 0L);
     REQUIRE(packed && frame && rays && xw && (level == 0 || level == 1) && N >= 0 && S >= 1 && ray_stride >= 8 && mode >= 0 && mode <= 2,
             "sahs_model_field_forward_split");
-    const bool x3 = precision == SAHS_BF16X3 && model == SAHS_MODEL_AUDIO;
+    const bool x3 = precision == SAHS_BF16X3, audio = model == SAHS_MODEL_AUDIO;
     const bool mixed = (precision == SAHS_BF16 && model == SAHS_MODEL_NERFACE) || x3;
     REQUIRE((mode == 1 || raw) && (mode == 2 || z) && (mode != 2 || src || mixed), "sahs_model_field_forward_split(buffers of the mode)");
     REQUIRE(xw_col0 >= 0 && xw_row >= xw_col0 + (mode == 2 ? 0 : S) && ALIGNED16(xw) && ALIGNED16(packed) && ALIGNED16(frame) && (!raw || ALIGNED16(raw)),
             "sahs_model_field_forward_split(xw layout / alignment)");
     hipStream_t st = (hipStream_t)stream;
-    if (mixed) {      // deformation nets by the fp32 kernel, radiance nets by the bf16 kernel; mode 0 = both, one after the other
-        const float *pk16 = (const float *)packed, *pk32 = pk16 + (x3 ? sahs_layout_packed_words_bf16x3() : sahs_layout_packed_words_bf16_nf());
+    if (mixed) {      // deformation launch, then radiance launch (mode 0 = both, one after the other)
+        // packed: SAHS_BF16X3 [hi/lo streams | fp32 pack]; the NeRFaceModel's mixed precision [bf16 radiance pack | fp32 pack | hi/lo streams]
+        const float *pk16 = (const float *)packed;
+        const float *pk32 = pk16 + (x3 ? (audio ? sahs_layout_packed_words_bf16x3() : sahs_layout_packed_words_bf16x3_nf()) : sahs_layout_packed_words_bf16_nf());
         REQUIRE(mode != 0 || xw_col0 == 0, "sahs_model_field_forward_split(mixed precision, mode 0: xw_col0 must be 0)");
         int e = 0;
         // the deformation nets run on the split-operand pipe (field_bf16x3.hip; round 3 -- SAHS_X3_DEFORM=f32 in the environment keeps them
-        // on the fp32 kernel, the A/B reference and the form round 2 shipped): SAHS_BF16X3 of the AudioFaceModel, and the mixed-precision
-        // NeRFaceModel, whose radiance nets are plain bf16 anyway
+        // on the fp32 kernel, the A/B reference and the form round 2 shipped): SAHS_BF16X3, and the mixed-precision NeRFaceModel, whose
+        // radiance nets are plain bf16 anyway
         const bool x3_deform_f32 = x3_deform_on_f32();
         if (mode != 2 && !x3_deform_f32)
-            e = probed(probe_kind(model, x3 ? precision : SAHS_BF16X3, level, 1), N * S, st, [&] {
-                return x3 ? sahs_field_deform_bf16x3_launch(pk16, frame, level, N * S, S, rays, ray_stride, z, xw, xw_row, xw_col0, num_cus(), st)
-                          : sahs_field_deform_bf16x3_launch_nf(pk16 + nf_mixed_x3_off(), frame, level, N * S, S, rays, ray_stride, z, xw, xw_row, xw_col0,
-                                                               num_cus(), st);
+            e = probed(probe_kind(model, SAHS_BF16X3, level, 1), N * S, st, [&] {
+                return x3 && audio ? sahs_field_deform_bf16x3_launch(pk16, frame, level, N * S, S, rays, ray_stride, z, xw, xw_row, xw_col0, num_cus(), st)
+                                   : sahs_field_deform_bf16x3_launch_nf(pk16 + (x3 ? 0 : nf_mixed_x3_off()), frame, level, N * S, S, rays, ray_stride, z, xw,
+                                                                        xw_row, xw_col0, num_cus(), st);
             });
         else if (mode != 2)
             e = probed(probe_kind(model, SAHS_F32, level, 1), N * S, st, [&] {
-                return x3 ? sahs_field_forward_f32_split_launch(pk32, frame, level, 1, N * S, S, rays, ray_stride, z, nullptr, xw, xw_row, xw_col0, nullptr,
-                                                                nullptr, num_cus(), st)
-                          : sahs_field_forward_f32_split_launch_nf(pk32, frame, level, 1, N * S, S, rays, ray_stride, z, nullptr, xw, xw_row, xw_col0, nullptr,
-                                                                   nullptr, num_cus(), st);
+                return audio ? sahs_field_forward_f32_split_launch(pk32, frame, level, 1, N * S, S, rays, ray_stride, z, nullptr, xw, xw_row, xw_col0, nullptr,
+                                                                   nullptr, num_cus(), st)
+                             : sahs_field_forward_f32_split_launch_nf(pk32, frame, level, 1, N * S, S, rays, ray_stride, z, nullptr, xw, xw_row, xw_col0, nullptr,
+                                                                      nullptr, num_cus(), st);
             });
         if (!e && mode != 1)
             e = probed(probe_kind(model, precision, level, 2), N * S, st, [&] {
-                return x3 ? sahs_field_radiance_bf16x3_launch(pk16, frame, level, N * S, S, rays, ray_stride, raw, xw, xw_row, mode == 2 ? src : nullptr,
-                                                              num_cus(), st)
-                          : sahs_field_forward_bf16w_split_launch_nf(pk16, frame, level, 2, N * S, S, rays, ray_stride, nullptr, raw, xw, xw_row, 0,
-                                                                     mode == 2 ? src : nullptr, num_cus(), st);
+                const int *sp = mode == 2 ? src : nullptr;
+                return !x3   ? sahs_field_forward_bf16w_split_launch_nf(pk16, frame, level, 2, N * S, S, rays, ray_stride, nullptr, raw, xw, xw_row, 0, sp,
+                                                                        num_cus(), st)
+                       : audio ? sahs_field_radiance_bf16x3_launch(pk16, frame, level, N * S, S, rays, ray_stride, raw, xw, xw_row, sp, num_cus(), st)
+                               : sahs_field_radiance_bf16x3_launch_nf(pk16, frame, level, N * S, S, rays, ray_stride, raw, xw, xw_row, sp, num_cus(), st);
             });
         return e ? hip_fail("sahs_model_field_forward_split", e) : 0;
     }
@@ -800,7 +838,9 @@ int sahs_model_field_forward_split_save_bits_x3(int model, const void *packed, c
                                                 float *act_out, uint32_t *bits_out, void *stream)
 {
     const char *who = "sahs_model_field_forward_split_save_bits_x3";
-    REQUIRE(model == SAHS_MODEL_AUDIO, "sahs_model_field_forward_split_save_bits_x3(AudioFaceModel only)");
+    REQUIRE_MODEL(model, who);
+    if (model == SAHS_MODEL_NERFACE_STATIC)
+        return fail(4, "%s: this model has no deformation nets (its saving forward on this pipe: sahs_model_field_forward_save_bits_x3)%ld", who, 0L);
     if (N == 0) return 0;
     REQUIRE(packed && frame && rays && xw && act_out && bits_out && (level == 0 || level == 1) && N >= 0 && S >= 1 && ray_stride >= 8 && (mode == 1 || mode == 2),
             "sahs_model_field_forward_split_save_bits_x3(mode 1 = deformation nets or 2 = radiance nets)");
@@ -811,11 +851,36 @@ int sahs_model_field_forward_split_save_bits_x3(int model, const void *packed, c
     REQUIRE(P <= 4000000L, "sahs_model_field_forward_split_save_bits_x3(at most 4e6 samples per call)");
     float *base = act_out - act_col0(model, mode) * P;
     hipStream_t st = (hipStream_t)stream;
+    const bool audio = model == SAHS_MODEL_AUDIO;
     int e = probed(probe_kind(model, SAHS_BF16X3, level, mode), P, st, [&] {
-        return mode == 1 ? sahs_field_deform_bf16x3_save_launch((const float *)packed, frame, level, P, S, rays, ray_stride, z, xw, xw_row, xw_col0, base, bits_out,
-                                                                num_cus(), st)
-                         : sahs_field_radiance_bf16x3_save_launch((const float *)packed, frame, level, P, S, rays, ray_stride, raw, xw, xw_row, src, base, bits_out,
-                                                                  num_cus(), st);
+        const float *pk = (const float *)packed;
+        if (mode == 1)
+            return (audio ? sahs_field_deform_bf16x3_save_launch : sahs_field_deform_bf16x3_save_launch_nf)(pk, frame, level, P, S, rays, ray_stride, z, xw, xw_row,
+                                                                                                            xw_col0, base, bits_out, num_cus(), st);
+        return (audio ? sahs_field_radiance_bf16x3_save_launch : sahs_field_radiance_bf16x3_save_launch_nf)(pk, frame, level, P, S, rays, ray_stride, raw, xw, xw_row,
+                                                                                                            src, base, bits_out, num_cus(), st);
+    });
+    return e ? hip_fail(who, e) : 0;
+}
+
+// the whole-network saving forward on the split-operand pipe: the buffers of sahs_model_field_forward_save_bits written by the SAHS_BF16X3
+// kernel (`packed` = that precision's weights).  The NeRFaceModel without deformation nets; the others save through the split form
+int sahs_model_field_forward_save_bits_x3(int model, const void *packed, const float *frame, int level, long N, int S, const float *rays, int ray_stride,
+                                          const float *z, float *raw, float *act_out, uint32_t *bits_out, void *stream)
+{
+    const char *who = "sahs_model_field_forward_save_bits_x3";
+    REQUIRE_MODEL(model, who);
+    if (model != SAHS_MODEL_NERFACE_STATIC)
+        return fail(4, "%s: this model saves through the split chain on this pipe (sahs_model_field_forward_split_save_bits_x3)%ld", who, 0L);
+    REQUIRE(packed && frame && rays && z && raw && act_out && bits_out, who);
+    REQUIRE((level == 0 || level == 1) && N >= 0 && S >= 1 && ray_stride >= 8, "sahs_model_field_forward_save_bits_x3(shape)");
+    REQUIRE(ALIGNED16(packed) && ALIGNED16(frame) && ALIGNED16(raw) && ALIGNED16(act_out) && ALIGNED16(bits_out), "sahs_model_field_forward_save_bits_x3(alignment)");
+    const long P = N * S;
+    REQUIRE(P <= 4000000L, "sahs_model_field_forward_save_bits_x3(at most 4e6 samples per call)");
+    if (P == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    int e = probed(probe_kind(model, SAHS_BF16X3, level, 0), P, st, [&] {
+        return sahs_field_forward_bf16x3_save_launch_ns((const float *)packed, frame, level, P, S, rays, ray_stride, z, raw, act_out, bits_out, num_cus(), st);
     });
     return e ? hip_fail(who, e) : 0;
 }
@@ -891,10 +956,8 @@ int sahs_model_render_rays_rows(int model, const void *packed, const float *fram
     REQUIRE_MODEL(model, "sahs_model_render_rays_rows");
     if (N == 0) return 0;
     REQUIRE(rows && row_ld >= SAHS_ROW_COLUMNS, "sahs_model_render_rays_rows(rows)");
-    if ((precision == SAHS_BF16 && model == SAHS_MODEL_NERFACE) || precision == SAHS_BF16X3) {
+    if (model != SAHS_MODEL_NERFACE_STATIC && ((precision == SAHS_BF16 && model == SAHS_MODEL_NERFACE) || precision == SAHS_BF16X3))
         REQUIRE(xw && src && z_new && nf > 0, "sahs_model_render_rays_rows(a mixed-precision model needs the xw / src / z_new workspace and nf > 0)");
-        REQUIRE(precision != SAHS_BF16X3 || model == SAHS_MODEL_AUDIO, "sahs_model_render_rays_rows(SAHS_BF16X3 is built for SAHS_MODEL_AUDIO)");
-    }
     if (xw && src && z_new && nf > 0 && model != SAHS_MODEL_NERFACE_STATIC &&
         (precision == SAHS_F32 || precision == SAHS_BF16 || precision == SAHS_BF16X3
          )) {

@@ -1,4 +1,4 @@
-// field_bf16x3.hip -- near-fp32 radiance nets on the bf16 matrix pipe (precision SAHS_BF16X3).
+// field_bf16x3.hip -- near-fp32 field nets on the bf16 matrix pipe (precision SAHS_BF16X3), every model.
 //
 // Every operand is split into two bf16 numbers, x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (16-17 significant bits together),
 // and a product is three MFMAs with fp32 accumulation,
@@ -9,7 +9,7 @@
 //   * TWO KERNELS for the split evaluation's launches: field_radiance_bf16x3_kernel (FIELD_RADIANCE) and, since round 3,
 //     field_deform_bf16x3_kernel (FIELD_DEFORM; round 2 left the deformation nets on the fp32 kernel because the deformed point feeds
 //     sin/cos(2^9 x') -- measured, the split-operand error on x' = x + tanh(.) is 6e-7 and the frame stays within 4x the fp32 tolerance;
-//     see the kernel's header).  AudioFaceModel only.
+//     see the kernel's header).
 //   * ONE 32-sample half per wave: an activation block holds hi AND lo fragments -- the registers two halves of plain bf16 would take.
 //   * The packed stream holds [hi fragment | lo fragment] per k-step (2 KB), so a 64 KB chunk holds half as many tiles.
 //   * The conversion produces hi and lo (about 5 VALU per value instead of 2.5); with three MFMAs per value it hides under them.
@@ -20,24 +20,24 @@
 #include "bf16_pipe.hpp"
 #include "bf16x3_pipe.hpp"      // Blk, dense_x, dense_x_out, the conversion ticks and their epilogue policies
 
-#if SAHS_MODEL == 2
-#error "field_bf16x3.hip: the model without deformation nets has no use for it (its whole net is the plain-bf16 radiance kernel)"
-#endif
-// SAHS_MODEL 0 (AudioFaceModel): both kernels = precision SAHS_BF16X3.  SAHS_MODEL 1 (NeRFaceModel with deformation nets): the deformation
-// kernel only -- the deformation launches of that model's mixed-precision path (SAHS_BF16), whose radiance nets are plain bf16 anyway.
-
+// One source for every model (sahs_model.hpp), written against the layout constants as field_bf16w.hip is:
+//   SAHS_MODEL 0 (AudioFaceModel) and 1 (NeRFaceModel with deformation nets): both kernels -- the split chain's deformation and radiance
+//     launches.  Model 1's mixed precision (SAHS_BF16) also uses the deformation kernel, beside plain-bf16 radiance nets.
+//   SAHS_MODEL 2 (NeRFaceModel without deformation nets): the radiance kernel is the whole network, queried at the raw point x = o + d z.
 namespace SAHS_NS {
 namespace hx3 {
 
 // ---- positional encoding (v_sin_f32 on an fp32 revolution count reduced exactly: the value keeps ~fp32 accuracy, then hi/lo split) ------
+constexpr int KX32 = (KB_XYZ + 1) / 2, KA32 = (KB_AMB + 1) / 2;      // 32-feature blocks of PE(x') and PE(w): 2, 1 | 3, 1 | 2, 0
+static_assert(KB_XYZ % 2 == 0 && KB_AMB % 2 == 0, "a saved encoding plane is a whole number of 32-feature blocks");
 struct PeSlot { float scale; float phase; int axis; int kind; };   // kind: 0 zero pad, 1 raw input, 2 sinusoid
-template <int D, int L>
+template <int D, int L, int INC = 1>      // INC: the encoding starts with its input (nerf_helpers.py:305-349 include_input)
 constexpr PeSlot pe_slot(int f)
 {
-    constexpr int W = D + 2 * D * L;
+    constexpr int W = INC * D + 2 * D * L;
     if (f >= W) return PeSlot{0.0f, 0.0f, 0, 0};
-    if (f < D) return PeSlot{1.0f, 0.0f, f, 1};
-    const int g = f - D, k = g / (2 * D), rem = g % (2 * D);
+    if (INC && f < D) return PeSlot{1.0f, 0.0f, f, 1};
+    const int g = f - INC * D, k = g / (2 * D), rem = g % (2 * D);
     return PeSlot{(float)(1 << k), (rem / D) ? 0.25f : 0.0f, rem % D, 2};
 }
 // sin(2 pi t) for t = 2^k u + phase with u = x / (2 pi) held as an unevaluated fp32 sum (uh + ul): the product by a power of two and the
@@ -51,7 +51,7 @@ __device__ __forceinline__ float sin_rev(float uh, float ul, float scale, float 
 }
 // save (optional): this lane's slot of the sample's row of the encoding's saved-activation plane (row + 4 h floats): the fp32 values, natural
 // feature order -- what the backward's PE derivative and weight-gradient jobs read (training with the forward on this pipe)
-template <int D, int L, int NB>
+template <int D, int L, int NB, int INC = 1>
 __device__ __forceinline__ void pe_blocks_x(const float *v, int h, Blk *out, float *save = nullptr)
 {
     float uh[3], ul[3];
@@ -69,7 +69,7 @@ __device__ __forceinline__ void pe_blocks_x(const float *v, int h, Blk *out, flo
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int f0 = 32 * b + 16 * s + 8 * (j >> 2) + (j & 3);
-                const PeSlot a = pe_slot<D, L>(f0), c = pe_slot<D, L>(f0 + 4);   // lane half 0 / 1
+                const PeSlot a = pe_slot<D, L, INC>(f0), c = pe_slot<D, L, INC>(f0 + 4);   // lane half 0 / 1
                 if (a.kind == 0 && c.kind == 0) {
                     r[j] = 0.0f;
                 } else {
@@ -110,7 +110,7 @@ __device__ __forceinline__ auto layer_policy(float slope, float *actbuf, uint32_
 
 #define CHX(id) (pick_GX(kProgH.layer[id].KB32, kProgH.layer[id].NT32) * kProgH.layer[id].KB32 * 2048)   /* halfwords in one chunk of layer id */
 
-#if SAHS_MODEL == 0      // ---- the radiance kernel (AudioFaceModel) ----
+// ---- the radiance kernel ----
 // trilinear lookup (fp32, ATen corner order, zeros padding); this lane takes channels 16s + 8g + 4h + 0..3
 __device__ __forceinline__ void grid_block_x(const float *__restrict__ grid, float x, float y, float z, int h, Blk &out, float *save = nullptr)
 {
@@ -155,19 +155,29 @@ __device__ __forceinline__ void grid_block_x(const float *__restrict__ grid, flo
 
 
 // The radiance nets of `level` on S samples per ray whose (x', w) are xw[ray][src ? src[ray][s] : s] (field_f32.hip, FIELD_RADIANCE).
+// Model 2 (no deformation nets): the whole network (field_f32.hip, FIELD_ALL) at the raw point x = rays[ray][0:3] + rays[ray][3:6] zvals[p],
+// no ambient coordinate; xw, src unused.  Models 0, 1: zvals unused.
 // SAVE (training with the forward on this pipe): also the saved activations of the radiance part (actbuf: column c of the act:: table at
-// actbuf + c * P) and its sign-bit planes (bits), exactly the buffers field_forward_f32_kernel<true, 2> writes for the backward.
+// actbuf + c * P) and its sign-bit planes (bits), exactly the buffers field_forward_f32_kernel<true, 2> (model 2: <true, 0>) writes for
+// the backward -- the point in act::XW included, which the grid backward reads.
 template <bool SAVE>
 __global__ void __launch_bounds__(X_THREADS, 1)
 field_radiance_bf16x3_kernel(const float *__restrict__ packed, const float *__restrict__ frame, int level, long P, int S,
-                             const float *__restrict__ rays, int ray_stride, float *__restrict__ raw, const float *__restrict__ xw, int xw_row,
-                             const int *__restrict__ src, float *__restrict__ actbuf, uint32_t *__restrict__ bits)
+                             const float *__restrict__ rays, int ray_stride, const float *__restrict__ zvals, float *__restrict__ raw,
+                             const float *__restrict__ xw, int xw_row, const int *__restrict__ src, float *__restrict__ actbuf,
+                             uint32_t *__restrict__ bits)
 {
     constexpr uint32_t RAD_OFF = (uint32_t)(2 * kProgH.layer[H_T0].stream_off);
-    // SAVE: the four staging tiles of the epilogue (bf16x3_pipe.hpp: SaveAct) -- wave 0's where the deformation nets' biases would be, the
-    // others' from the x', w stash on (those five values stay in registers instead) to the end of the 160 KB
+    // SAVE: the four staging tiles of the epilogue (bf16x3_pipe.hpp: SaveAct).  The point's five values stay in registers, so the x', w
+    // stash is free for them from its start to the end of the 160 KB.  Where the deformation nets' biases would be (models 0, 1: 4,736
+    // bytes, which this launch does not load) holds wave 0's: the stash area alone has room for only three tiles beside the AudioFaceModel's
+    // larger bias array.  Model 2 has no deformation biases: all four tiles in the stash area.
     constexpr int RAD_BIAS0 = kProgH.layer[H_T0].bias_off;
-    static_assert(!SAVE || (RAD_BIAS0 * 4 >= SAVE_WAVE_BYTES && LDS_STASH_BYTE_OFF + (X_THREADS / WAVE - 1) * SAVE_WAVE_BYTES <= LDS_BYTES_SAVE), "staging tiles of the saving radiance kernel");
+    constexpr bool TILE0_IN_BIAS = RAD_BIAS0 * 4 >= SAVE_WAVE_BYTES;
+    constexpr int STASH_TILES = X_THREADS / WAVE - (TILE0_IN_BIAS ? 1 : 0);
+    static_assert(!SAVE || LDS_STASH_BYTE_OFF + STASH_TILES * SAVE_WAVE_BYTES <= LDS_BYTES_SAVE, "staging tiles of the saving radiance kernel");
+    static_assert(USE_DEFORM || (!TILE0_IN_BIAS && LDS_STASH_BYTE_OFF + (X_THREADS / WAVE) * SAVE_WAVE_BYTES <= LDS_BYTES_SAVE),
+                  "model 2: all four 4,608-byte staging tiles fit behind its biases in the 160 KB");
     extern __shared__ __attribute__((aligned(16))) char lds_x[];
     Ctx cx;
     cx.stream = reinterpret_cast<const unsigned short *>(packed + PACKX_STREAM_OFF) + (long)level * STREAM_HWX;
@@ -206,8 +216,9 @@ field_radiance_bf16x3_kernel(const float *__restrict__ packed, const float *__re
         if constexpr (SAVE) asm volatile("" : "+s"(Pq));      // (the ~25 plane bases c * P: keep them from being hoisted out of the tile loop and spilled)
         SaveStage sst;
         if constexpr (SAVE)
-            sst = make_save_stage(lds_x, cx.wave == 0 ? (uint32_t)LDS_BIAS_BYTE_OFF : (uint32_t)(LDS_STASH_BYTE_OFF + (cx.wave - 1) * SAVE_WAVE_BYTES), cx.lane,
-                                  tile * X_PTS_PER_WG + cx.wave * X_PTS_PER_WAVE, p, P);
+            sst = make_save_stage(lds_x, TILE0_IN_BIAS ? (cx.wave == 0 ? (uint32_t)LDS_BIAS_BYTE_OFF : (uint32_t)(LDS_STASH_BYTE_OFF + (cx.wave - 1) * SAVE_WAVE_BYTES))
+                                                       : (uint32_t)(LDS_STASH_BYTE_OFF + cx.wave * SAVE_WAVE_BYTES),
+                                  cx.lane, tile * X_PTS_PER_WG + cx.wave * X_PTS_PER_WAVE, p, P);
 #define pol(slope, c, width, boff) layer_policy<SAVE, width, 0>(slope, actbuf, bits, Pq, sst, c, boff)
 #define pol_nosign(slope, c, width) layer_policy<SAVE, width, -1>(slope, actbuf, bits, Pq, sst, c, 0)
 #define plane(c, width) (SAVE ? actbuf + (long)(c) * Pq + p * (width) + 4 * h : nullptr)
@@ -216,15 +227,25 @@ field_radiance_bf16x3_kernel(const float *__restrict__ packed, const float *__re
         float sxw[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #define xwv(i) (SAVE ? sxw[i] : stash[i])      /* x'[3], w[2] of this lane's sample: SAVE in registers (both lanes of the sample load them), else parked in LDS */
         if (SAVE || h == 0) {
-            const float *row = xw + ((p / S) * (long)xw_row + (src != nullptr ? src[p] : (int)(p % S))) * 8;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(row);
+            f32x4 v;
+            float v4;
+            if constexpr (USE_DEFORM) {      // x', w from the launches that deformed these samples
+                const float *row = xw + ((p / S) * (long)xw_row + (src != nullptr ? src[p] : (int)(p % S))) * 8;
+                v = *reinterpret_cast<const f32x4 *>(row);
+                v4 = row[4];
+            } else {                         // models.py:316-327 with use_warp False, use_ambient False: x' = x (train_utils.py:115), no w
+                const float *rp = rays + (p / S) * ray_stride;
+                const float z = zvals[p];
+                v = f32x4{rp[0] + rp[3] * z, rp[1] + rp[4] * z, rp[2] + rp[5] * z, 0.0f};
+                v4 = 0.0f;
+            }
             if constexpr (SAVE) {
                 sxw[0] = v[0]; sxw[1] = v[1]; sxw[2] = v[2]; sxw[3] = v[3];
-                sxw[4] = row[4];
+                sxw[4] = v4;
                 if (h == 0) { float *d = actbuf + (long)act::XW * Pq + p * 16; d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; }      // the grid backward reads x'
             } else {
                 stash[0] = v[0]; stash[1] = v[1]; stash[2] = v[2]; stash[3] = v[3];
-                stash[4] = row[4];
+                stash[4] = v4;
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -234,23 +255,26 @@ field_radiance_bf16x3_kernel(const float *__restrict__ packed, const float *__re
             Blk B[8];
             const auto e0 = pol(0.01f, act::T, 256, sbits::BR_T);
             {
-                Blk in_tr[3];
+                Blk in_tr[KX32 + KA32];
                 const float xp[3] = {xwv(0), xwv(1), xwv(2)}, amb[3] = {xwv(3), xwv(4), 0.0f};
-                pe_blocks_x<3, 10, 2>(xp, h, in_tr, plane(act::PEX, 64));
-                pe_blocks_x<2, 4, 1>(amb, h, in_tr + 2, plane(act::PEW, 32));
-                dense_x<2, 1, 0, 8, CHX(H_T1), false>(cx, st, in_tr, in_tr + 2, nullptr, A, Ly[H_T0].bias_off, e0, FwdAct{1.0f});
+                pe_blocks_x<3, L_XYZ, KX32>(xp, h, in_tr, plane(act::PEX, 16 * KB_XYZ));
+                if constexpr (KA32 > 0) pe_blocks_x<(AMB_DIM > 0 ? AMB_DIM : 1), L_AMB, KA32, AMB_INC>(amb, h, in_tr + KX32, plane(act::PEW, 16 * KB_AMB));
+                dense_x<KX32, KA32, 0, 8, CHX(H_T1), false>(cx, st, in_tr, in_tr + KX32, nullptr, A, Ly[H_T0].bias_off, e0, FwdAct{1.0f});
             }
             const auto e1 = pol(0.01f, act::T + 256, 256, sbits::BR_T + 8);
             dense_x<8, 0, 0, 8, CHX(H_T2), true, 7>(cx, st, A, nullptr, nullptr, B, Ly[H_T1].bias_off, e1, e0);
             const auto e2 = pol(0.01f, act::T + 512, 256, sbits::BR_T + 16);
             dense_x<8, 0, 0, 8, CHX(H_T3), true, 7>(cx, st, B, nullptr, nullptr, A, Ly[H_T2].bias_off, e2, e1);
             {   // the re-injected encoding [PE(x') | PE(w)] is rebuilt at the skip layer instead of staying live
-                Blk in_tr[3];
+                Blk in_tr[KX32 + KA32];
                 const float xp[3] = {xwv(0), xwv(1), xwv(2)}, amb[3] = {xwv(3), xwv(4), 0.0f};
-                pe_blocks_x<3, 10, 2>(xp, h, in_tr);
-                pe_blocks_x<2, 4, 1>(amb, h, in_tr + 2);
-                dense_x<8, 2, 1, 8, CHX(H_T4), true, 7>(cx, st, A, in_tr, in_tr + 2, B, Ly[H_T3].bias_off, pol(0.01f, act::T + 768, 256, sbits::BR_T + 24), e2);
+                pe_blocks_x<3, L_XYZ, KX32>(xp, h, in_tr);
+                if constexpr (KA32 > 0) pe_blocks_x<(AMB_DIM > 0 ? AMB_DIM : 1), L_AMB, KA32, AMB_INC>(amb, h, in_tr + KX32);
+                // (the next layer: T4, or fc_feat in the NeRFaceModels' 4-layer trunk, whose skip layer is its last -- modules.py:176)
+                dense_x<8, KX32, KA32, 8, CHX(H_T3 + 1), true, 7>(cx, st, A, in_tr, in_tr + KX32, B, Ly[H_T3].bias_off,
+                                                               pol(0.01f, act::T + 768, 256, sbits::BR_T + 24), e2);
             }
+#if SAHS_MODEL == 0
 #pragma unroll 1
             for (int j = 0; j < 2; ++j) {     // T4, T5 | T6, T7 (identical shapes: one copy of the code, run twice)
                 const auto ea = pol(0.01f, act::T + 256 * (4 + 2 * j), 256, sbits::BR_T + 8 * (4 + 2 * j));
@@ -259,8 +283,9 @@ field_radiance_bf16x3_kernel(const float *__restrict__ packed, const float *__re
                 dense_x<8, 0, 0, 8, CHX(H_T5), true, 7>(cx, st, A, nullptr, nullptr, B, Ly[H_T4].bias_off + 512 * j + 256,
                                                        pol(0.01f, act::T + 256 * (5 + 2 * j), 256, sbits::BR_T + 8 * (5 + 2 * j)), ea);
             }
+#endif
             dense_x<8, 0, 0, 8, CHX(H_ALPHA), true, 7>(cx, st, B, nullptr, nullptr, A, Ly[H_FEAT].bias_off, pol_nosign(1.0f, act::FEAT, 256),
-                                                      pol(0.01f, act::T + 256 * 7, 256, sbits::BR_T + 8 * 7));
+                                                      pol(0.01f, act::T + 256 * (TR_LAYERS - 1), 256, sbits::BR_T + 8 * (TR_LAYERS - 1)));
         }
         dense_x_out<8, CHX(H_D0), 7>(cx, st, A, fin, Ly[H_ALPHA].bias_off, true, pol_nosign(1.0f, act::FEAT, 256));
         {   // colour branch
@@ -305,8 +330,8 @@ field_radiance_bf16x3_kernel(const float *__restrict__ packed, const float *__re
 #undef xwv
 #undef pol_nosign
 #undef plane
-#endif      // SAHS_MODEL == 0
 
+#if SAHS_MODEL != 2
 // The deformation nets (warp field + hyper sheet, level-independent inputs) on the depths zvals: x' = x + tanh(warp(PE(x))), w = hyper(PE(x))
 // to xw[ray][xw_col0 + s] (field_f32.hip, FIELD_DEFORM; same arguments).  Round 3: with these launches on the split-operand pipe too the
 // bf16x3 frame no longer contains an fp32-MFMA launch.  What that costs in accuracy was measured before it was built
@@ -314,7 +339,7 @@ field_radiance_bf16x3_kernel(const float *__restrict__ packed, const float *__re
 // from 1.7e-5 to 2.8e-5 of the fp32 frame at worst -- inside four times the fp32 tolerance for every ray, the criterion of
 // tests/test_gpu_bf16.py -- because x' = x + tanh(.) adds a SMALL correction to an exact x: the 6e-6 relative error of the nets lands on
 // |dx| << 1, not on x' itself, before sin(2^9 x') amplifies it.
-// SAVE (training with the forward on this pipe, AudioFaceModel): also the saved activations and sign-bit planes of the deformation part, the
+// SAVE (training with the forward on this pipe): also the saved activations and sign-bit planes of the deformation part, the
 // buffers field_forward_f32_kernel<true, 1> writes for the backward.
 template <bool SAVE>
 __global__ void __launch_bounds__(X_THREADS, 1)
@@ -371,7 +396,6 @@ field_deform_bf16x3_kernel(const float *__restrict__ packed, const float *__rest
 #pragma unroll
             for (int i = 0; i < 3; ++i) x[i] = rp[i] + rp[3 + i] * z;
         }
-        constexpr int KX32 = (KB_XYZ + 1) / 2;        // 32-feature blocks of PE(x): 2 (10 octaves) | 3 (15 octaves, NeRFaceModel)
         Blk pe_x[KX32];
         pe_blocks_x<3, L_XYZ, KX32>(x, h, pe_x, SAVE ? actbuf + (long)act::E * Pq + p * (16 * KB_XYZ) + 4 * h : nullptr);
         {   // warp field (models.py:296-305; layers alternate between two register sets)
@@ -429,16 +453,16 @@ field_deform_bf16x3_kernel(const float *__restrict__ packed, const float *__rest
 }
 
 #undef pold
+#endif      // SAHS_MODEL != 2
 }  // namespace hx3
 }  // namespace SAHS_NS
 
 using namespace SAHS_NS;
 using namespace SAHS_NS::hx3;
 
-#if SAHS_MODEL == 0
 template <bool SAVE>
-static int launch_radiance_x3(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, float *raw,
-                              const float *xw, int xw_row, const int *src, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream)
+static int launch_radiance_x3(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, const float *zvals,
+                              float *raw, const float *xw, int xw_row, const int *src, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream)
 {
     if (P <= 0) return 0;
     if (SAVE && P * (long)(4 * 256) >= (1L << 32)) return -4;      // (SaveAct: 32-bit byte offsets inside a layer's plane)
@@ -449,26 +473,44 @@ static int launch_radiance_x3(const float *packed, const float *frame, int level
         return hipFuncSetAttribute(reinterpret_cast<const void *>(field_radiance_bf16x3_kernel<SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, SAVE ? LDS_BYTES_SAVE : LDS_BYTES);
     });
     if (ae != hipSuccess) return (int)ae;
-    field_radiance_bf16x3_kernel<SAVE><<<grid, X_THREADS, SAVE ? LDS_BYTES_SAVE : LDS_BYTES, stream>>>(packed, frame, level, P, S, rays, ray_stride, raw, xw, xw_row, src, actbuf, bits);
+    field_radiance_bf16x3_kernel<SAVE><<<grid, X_THREADS, SAVE ? LDS_BYTES_SAVE : LDS_BYTES, stream>>>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, xw,
+                                                                                                      xw_row, src, actbuf, bits);
     return (int)hipGetLastError();
 }
+#if SAHS_MODEL != 2
 // the radiance launch of the split evaluation (field_f32.hip: sahs_field_forward_f32_split_launch mode 2, same arguments)
-extern "C" int sahs_field_radiance_bf16x3_launch(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                                 int ray_stride, float *raw, const float *xw, int xw_row, const int *src, int num_cu,
-                                                 hipStream_t stream)
+extern "C" int SAHS_SYM(sahs_field_radiance_bf16x3_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
+                                                           int ray_stride, float *raw, const float *xw, int xw_row, const int *src, int num_cu,
+                                                           hipStream_t stream)
 {
-    return launch_radiance_x3<false>(packed, frame, level, P, S, rays, ray_stride, raw, xw, xw_row, src, nullptr, nullptr, num_cu, stream);
+    return launch_radiance_x3<false>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, xw, xw_row, src, nullptr, nullptr, num_cu, stream);
 }
 // ... that also saves what the backward reads (field_f32.hip: sahs_field_forward_f32_split_bits_launch mode 2 with actbuf and bits, same buffers)
-extern "C" int sahs_field_radiance_bf16x3_save_launch(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                                      int ray_stride, float *raw, const float *xw, int xw_row, const int *src, float *actbuf,
-                                                      uint32_t *bits, int num_cu, hipStream_t stream)
+extern "C" int SAHS_SYM(sahs_field_radiance_bf16x3_save_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
+                                                                int ray_stride, float *raw, const float *xw, int xw_row, const int *src, float *actbuf,
+                                                                uint32_t *bits, int num_cu, hipStream_t stream)
 {
     if (actbuf == nullptr || bits == nullptr) return -2;
-    return launch_radiance_x3<true>(packed, frame, level, P, S, rays, ray_stride, raw, xw, xw_row, src, actbuf, bits, num_cu, stream);
+    return launch_radiance_x3<true>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, xw, xw_row, src, actbuf, bits, num_cu, stream);
+}
+#else
+// model 2: the whole network on the depths zvals (field_f32.hip: sahs_field_forward_f32_launch without dbg / actbuf, same arguments)
+extern "C" int SAHS_SYM(sahs_field_forward_bf16x3_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
+                                                          int ray_stride, const float *zvals, float *raw, int num_cu, hipStream_t stream)
+{
+    return launch_radiance_x3<false>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, 0, nullptr, nullptr, nullptr, num_cu, stream);
+}
+// ... that also saves what the backward reads (field_f32.hip: sahs_field_forward_f32_split_bits_launch mode 0 with actbuf and bits, same buffers)
+extern "C" int SAHS_SYM(sahs_field_forward_bf16x3_save_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
+                                                               int ray_stride, const float *zvals, float *raw, float *actbuf, uint32_t *bits, int num_cu,
+                                                               hipStream_t stream)
+{
+    if (actbuf == nullptr || bits == nullptr) return -2;
+    return launch_radiance_x3<true>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, 0, nullptr, actbuf, bits, num_cu, stream);
 }
 #endif
 
+#if SAHS_MODEL != 2
 template <bool SAVE>
 static int launch_deform_x3(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, const float *zvals,
                             float *xw, int xw_row, int xw_col0, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream)
@@ -491,12 +533,12 @@ extern "C" int SAHS_SYM(sahs_field_deform_bf16x3_launch)(const float *packed, co
 {
     return launch_deform_x3<false>(packed, frame, level, P, S, rays, ray_stride, zvals, xw, xw_row, xw_col0, nullptr, nullptr, num_cu, stream);
 }
-#if SAHS_MODEL == 0
-extern "C" int sahs_field_deform_bf16x3_save_launch(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
-                                                    const float *zvals, float *xw, int xw_row, int xw_col0, float *actbuf, uint32_t *bits, int num_cu,
-                                                    hipStream_t stream)
+// ... that also saves what the backward reads (field_f32.hip: sahs_field_forward_f32_split_bits_launch mode 1 with actbuf and bits, same buffers)
+extern "C" int SAHS_SYM(sahs_field_deform_bf16x3_save_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
+                                                              int ray_stride, const float *zvals, float *xw, int xw_row, int xw_col0, float *actbuf,
+                                                              uint32_t *bits, int num_cu, hipStream_t stream)
 {
     if (actbuf == nullptr || bits == nullptr) return -2;
     return launch_deform_x3<true>(packed, frame, level, P, S, rays, ray_stride, zvals, xw, xw_row, xw_col0, actbuf, bits, num_cu, stream);
 }
-#endif
+#endif      // SAHS_MODEL != 2

@@ -181,18 +181,20 @@ class AudioFaceModel(_FieldModel):
 class NeRFaceModel(_FieldModel):
     """models.py:189-378: expression-driven (driving = the 76-d expression vector).  Two architectures, chosen by the config as
     the reference does (models.py:231,244): warp + hyper sheet on (config/expression/person_2.yml, person_3.yml) or both off
-    (person_1.yml).  fp32 rendering and training; precision="bf16" (the deforming architecture only) is MIXED precision: a
-    bf16-level error in the warp output would be 16 rad at the 15th octave, so the deformation nets run with every operand split into
-    bf16 hi + lo (three MFMAs per product: x' within 9e-7 of the fp32 kernel's; round 2 ran them on the fp32 kernel, SAHS_X3_DEFORM=f32
-    still does) while the radiance nets run on plain bf16 operands; rendering through run_one_iter_of_nerf only
-    (it needs the per-chunk workspace)."""
+    (person_1.yml).  fp32 rendering and training.  precision="bf16x3" (both architectures): every net with its operands split into
+    bf16 hi + lo, three MFMAs per product, as on the AudioFaceModel -- with deformation nets through the split chain (a deformation and a
+    radiance launch), without them one whole-network launch; ops.training_forward_precision("bf16x3") puts a fp32 model's saving forward
+    on the same kernels.  precision="bf16": plain bf16 operands; with deformation nets it is MIXED precision: a bf16-level error in the
+    warp output would be 16 rad at the 15th octave, so the deformation nets run with split operands (x' within 9e-7 of the fp32 kernel's;
+    round 2 ran them on the fp32 kernel, SAHS_X3_DEFORM=f32 still does) while the radiance nets run on plain bf16 operands (DESIGN.md
+    section 7b).  The split-chain precisions render through run_one_iter_of_nerf only (they need the per-chunk workspace)."""
 
     def __init__(self, cfg, precision="fp32"):
         super().__init__()
         deform = (bool(cfg.models.warp.use_warp), bool(cfg.models.hyper.use_ambient))
         if deform[0] != deform[1]:
             raise NotImplementedError("NeRFaceModel: warp and hyper sheet are built both on or both off (as in the shipped configs)")
-        if precision not in ("fp32", "f32", "bf16"):
-            raise NotImplementedError("NeRFaceModel: fp32, or bf16 (with deformation nets: mixed precision, those stay fp32)")
+        if precision not in ("fp32", "f32", "bf16", "bf16x3"):
+            raise NotImplementedError("NeRFaceModel: fp32, bf16 (with deformation nets: mixed precision) or bf16x3")
         self.arch = "nerface" if deform[0] else "nerface_static"
         self._build(cfg, precision)

@@ -24,7 +24,7 @@ PRECISIONS = {"fp32": SAHS_F32, "f32": SAHS_F32, "bf16": SAHS_BF16,
 def is_mixed(arch, precision):
     """Precisions that exist as the split chain only (a deformation launch with split bf16 operands -- fp32 under SAHS_X3_DEFORM=f32 -- and a
     low-precision radiance launch, exchanging x', w)."""
-    return (precision == SAHS_BF16 and arch == "nerface") or (precision == SAHS_BF16X3 and arch == "audio")
+    return (precision == SAHS_BF16 and arch == "nerface") or (precision == SAHS_BF16X3 and arch in ("audio", "nerface"))
 
 
 def _p(t):
@@ -364,20 +364,25 @@ class LaunchProbe:
 # ---------------------------------------------------------------------------------------------------------
 # training path
 # ---------------------------------------------------------------------------------------------------------
-def field_forward_save(packed, frame, level, rays, z, arch="audio", bits=None):
+def field_forward_save(packed, frame, level, rays, z, arch="audio", bits=None, precision=SAHS_F32):
     """fp32 field forward that also returns the saved activations for field_backward: ONE buffer of P * act_words floats laid out
     as a dense [P x width] plane per layer (plane c starts at float c * P; sahs_layout.hpp, namespace act) -- NOT one row per
     sample, so it can only be handed to field_backward whole, with the same P.  bits (alloc_sign_bits(P, FIELD_ALL, arch, device)):
-    also filled with the sign-bit planes (sahs_model_field_forward_save_bits) -- hand both to field_backward_split(..., 3, bits=bits)."""
+    also filled with the sign-bit planes (sahs_model_field_forward_save_bits) -- hand both to field_backward_split(..., 3, bits=bits).
+    precision SAHS_BF16X3 (the NeRFaceModel without deformation nets, bits required): the same buffers written by the split-operand
+    kernel (sahs_model_field_forward_save_bits_x3); `packed` is then pack_weights(flat, SAHS_BF16X3, arch)."""
     packed, frame, rays, z = _req(packed, "packed"), _req(frame, "frame"), _req(rays, "rays"), _req(z, "z")
     N, S = z.shape
+    x3 = int(precision) == SAHS_BF16X3
+    if int(precision) not in (SAHS_F32, SAHS_BF16X3) or (x3 and bits is None):
+        raise _lib.SahsError("field_forward_save: fp32, or SAHS_BF16X3 with the sign bits (bits=alloc_sign_bits(...))")
     raw = torch.empty(N, S, 16, dtype=torch.float32, device=z.device)
     act = torch.empty(N * S, _fn("act_words_per_sample", arch)[0](), dtype=torch.float32, device=z.device)
     if bits is not None:
         bits = _req(bits, "bits", torch.int32)
         if tuple(bits.shape) != (N * S, int(_fn("bits_words_part", arch)[0](FIELD_ALL))):
             raise _lib.SahsError("field_forward_save: bits must come from alloc_sign_bits(N * S, FIELD_ALL, arch, device)")
-        f, name = _fn("field_forward_save_bits", arch)
+        f, name = _fn("field_forward_save_bits_x3" if x3 else "field_forward_save_bits", arch)
         check(f(_p(packed), _p(frame), int(level), N, S, _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(act), _p(bits), _stream()), name)
         return raw, act
     f, name = _fn("field_forward_save", arch)
@@ -405,8 +410,8 @@ def field_forward_split_save(packed, frame, level, mode, rays, xw, z=None, src=N
     """field_forward_split (fp32) that also keeps the activations of the layers it runs -> (raw or None, act).  act is the part's
     own buffer, (P, act_words_part(mode)) floats as dense per-layer planes; only field_backward_split of the same part reads it.
     bits (from alloc_sign_bits, same mode): also filled -- hand it to field_backward_split with act.
-    precision SAHS_BF16X3 (AudioFaceModel, modes FIELD_DEFORM / FIELD_RADIANCE, bits required): the same buffers written by the
-    split-operand kernels; `packed` is then pack_weights(flat, SAHS_BF16X3).
+    precision SAHS_BF16X3 (the models with deformation nets, modes FIELD_DEFORM / FIELD_RADIANCE, bits required): the same buffers written
+    by the split-operand kernels; `packed` is then pack_weights(flat, SAHS_BF16X3, arch).
     whole=(act, bits) of a WHOLE-network save (FIELD_ALL shapes): the launch fills `mode`'s part of them instead of buffers of its own
     (a saved array of column c starts at c * P in every save), so a FIELD_DEFORM + FIELD_RADIANCE pair leaves what one FIELD_ALL launch
     leaves -> (raw or None, whole act)."""
@@ -434,8 +439,6 @@ def field_forward_split_save(packed, frame, level, mode, rays, xw, z=None, src=N
         bits = _req(bits, "bits", torch.int32)
         if tuple(bits.shape) != (N * S, int(bwords(int(mode)))):
             raise _lib.SahsError("field_forward_split_save: bits must come from alloc_sign_bits(N * S, mode, arch, device)")
-        if int(precision) == SAHS_BF16X3 and arch != "audio":
-            raise _lib.SahsError("field_forward_split_save: the split-operand saving forward is built for the AudioFaceModel only")
         f, name = _fn("field_forward_split_save_bits_x3" if int(precision) == SAHS_BF16X3 else "field_forward_split_save_bits", arch)
         check(f(_p(packed), _p(frame), int(level), int(mode), N, int(S), _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(xw), int(xw.shape[1]), int(xw_col0),
                 _p(src), _p(act), _p(bits), _stream()), name)
@@ -464,10 +467,11 @@ _FUSED_BACKWARD = os.environ.get("SAHS_BWD_FUSED", "1") != "0"
 
 
 def training_forward_precision(precision=None):
-    """Arithmetic of the SAVING forward launches of a training step (RenderRaysFn's kept path, AudioFaceModel): "fp32" (default: fp32 MFMAs,
-    the form the parity tests pin) or "bf16x3" (the split-operand kernels of the SAHS_BF16X3 frame, which then also write the saved
-    activations and sign bits; values within a few 1e-6 relative of the fp32 kernel's).  SAHS_TRAIN_FORWARD in the environment selects the
-    initial value.  None queries."""
+    """Arithmetic of the SAVING forward launches of a training step (RenderRaysFn's kept path, every architecture): "fp32" (default: fp32
+    MFMAs, the form the parity tests pin) or "bf16x3" (the split-operand kernels of the SAHS_BF16X3 frame, which then also write the saved
+    activations and sign bits; values within a few 1e-6 relative of the fp32 kernel's).  The models with deformation nets save through the
+    split chain (a deformation + a radiance launch), the NeRFaceModel without them through one whole-network launch.  SAHS_TRAIN_FORWARD in
+    the environment selects the initial value.  None queries."""
     global _TRAIN_FORWARD
     if precision is not None:
         if precision not in ("fp32", "bf16x3"):
@@ -698,8 +702,9 @@ class RenderRaysFn(torch.autograd.Function):
                 arch="audio", loss_target=None, loss_mask=None, loss_weights=None, packed_x3=None):
         """With loss_target (N,>=3), loss_mask (N,12), loss_weights (12,) the op also returns (loss, stats) of the Stage-I objective
         (stage1_loss_forward) and its backward forms that loss's gradient inside the composite backward kernels.
-        packed_x3 (pack_weights(flat, SAHS_BF16X3); AudioFaceModel, kept path): the saving forward launches run on the split-operand
-        kernels (training_forward_precision "bf16x3") -- the coarse pass as a deformation + a radiance launch into one whole-network save."""
+        packed_x3 (pack_weights(flat, SAHS_BF16X3, arch); kept path, every architecture): the saving forward launches run on the split-operand
+        kernels (training_forward_precision "bf16x3") -- with deformation nets the coarse pass as a deformation + a radiance launch into one
+        whole-network save, without them one whole-network launch per level."""
         frame = fold_conditioning(flat.detach(), audio.detach(), pose, arch=arch)
         ctx.arch = arch
         ctx.has_loss = loss_target is not None
@@ -726,7 +731,7 @@ class RenderRaysFn(torch.autograd.Function):
             xw = torch.empty(N, num_coarse + num_fine, 8, dtype=torch.float32, device=rays.device)
             sb = lambda samples, mode: alloc_sign_bits(samples, mode, arch, rays.device)      # (None: this architecture's backward reads none)
             bits_c, bits_d, bits_r = sb(N * num_coarse, FIELD_ALL), sb(N * num_fine, FIELD_DEFORM), sb(N * (num_coarse + num_fine), FIELD_RADIANCE)
-            x3 = packed_x3 is not None and arch == "audio" and bits_c is not None
+            x3 = packed_x3 is not None and bits_c is not None
             pk, prec = (packed_x3, SAHS_BF16X3) if x3 else (packed, SAHS_F32)
             if x3:
                 act_c = torch.empty(N * num_coarse, _fn("act_words_part", arch)[0](FIELD_ALL), dtype=torch.float32, device=rays.device)
@@ -752,11 +757,13 @@ class RenderRaysFn(torch.autograd.Function):
             sb = lambda samples: alloc_sign_bits(samples, FIELD_ALL, arch, rays.device) if arch == "nerface_static" else None
             z_c = stratified_depths(rays, num_coarse, lindisp, t_rand)
             bits_c = sb(N * num_coarse)
-            raw_c, act_c = field_forward_save(packed, frame, 0, rays, z_c, arch, bits=bits_c)
+            x3 = packed_x3 is not None and bits_c is not None
+            pk, prec = (packed_x3, SAHS_BF16X3) if x3 else (packed, SAHS_F32)
+            raw_c, act_c = field_forward_save(pk, frame, 0, rays, z_c, arch, bits=bits_c, precision=prec)
             rgb_c, disp_c, acc_c, w_c, _ = composite_forward(raw_c, z_c, rays, noise_c, bg, white_background)
             z_f = resample(z_c, w_c, num_fine, u)
             bits_f = sb(z_f.numel())
-            raw_f, act_f = field_forward_save(packed, frame, 1, rays, z_f, arch, bits=bits_f)
+            raw_f, act_f = field_forward_save(pk, frame, 1, rays, z_f, arch, bits=bits_f, precision=prec)
             rgb_f, disp_f, acc_f, w_f, depth_f = composite_forward(raw_f, z_f, rays, noise_f, bg, white_background)
             outs = (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, w_f[:, -1].contiguous(), depth_f)
             ctx.has_bits = bits_c is not None

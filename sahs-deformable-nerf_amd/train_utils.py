@@ -91,7 +91,7 @@ def predict_and_render_radiance(ray_batch, model, options, mode="train", driving
         # forms that loss's gradient inside its composite backward (ops.RenderRaysFn)
         # ops.training_forward_precision("bf16x3"): the saving forward of a batch that keeps its activations runs on the split-operand kernels
         packed_x3 = None
-        if ops.training_forward_precision() == "bf16x3" and arch == "audio" and nf > 0 and N <= ops.RenderRaysFn.BLOCK_RAYS:
+        if ops.training_forward_precision() == "bf16x3" and nf > 0 and N <= ops.RenderRaysFn.BLOCK_RAYS:
             packed_x3, _ = model.packed(ops.SAHS_BF16X3)
         return ops.RenderRaysFn.apply(flat, driving.to(torch.float32), pose.to(torch.float32), rays.detach(), bg, t_rand, noise_c, u, noise_f,
                                       packed, nc, nf, bool(opt.lindisp), bool(opt.white_background), arch, *(_loss or (None, None, None)), packed_x3)

@@ -1,7 +1,9 @@
 """bench.py's two training legs alone (configs[4]: fp32 backward products, and the default split-bf16 backward), optionally with the
 fused backward walk switched off (--per-layer) for a same-box A/B.  --arch nerface / nerface_static: the same two legs for the
 NeRFaceModels (bench.py has none): a 2,048-ray step of config/expression_hotpath.yml -- 64 + 64 samples, noise 0.1, the fused Stage-I
-loss, no optimiser -- with the deformation nets (person_2/3.yml) or without (person_1.yml).  Prints one JSON line."""
+loss, no optimiser -- with the deformation nets (person_2/3.yml) or without (person_1.yml).  --only x3fwd --arch nerface|nerface_static:
+the step with its saving forward on the split-operand kernels (ops.training_forward_precision "bf16x3") alternated with the fp32-forward
+step, --repeats times each, in one process.  Prints one JSON line."""
 import argparse
 import importlib
 import json
@@ -17,7 +19,7 @@ sys.path.insert(0, REPO)
 import bench  # noqa: E402
 
 
-def nerface_leg(pkg, dev, arch, rays=2048, steps=5, warmup=2, backward="bf16x3"):
+def nerface_leg(pkg, dev, arch, rays=2048, steps=5, warmup=2, backward="bf16x3", forward="fp32"):
     """One NeRFaceModel training step as training.train_step takes it (forward + backward through the HIP autograd op, the objective
     and its gradient inside the HIP launches), timed over `steps` after `warmup`: 2,048 rays x (64 coarse + 128 fine) samples."""
     W, Tr = pkg.weights, pkg.training
@@ -45,8 +47,9 @@ def nerface_leg(pkg, dev, arch, rays=2048, steps=5, warmup=2, backward="bf16x3")
         outs[8].backward()
         return outs[8]
 
-    before = pkg.ops.backward_gemm_precision()
+    before, fwd_before = pkg.ops.backward_gemm_precision(), pkg.ops.training_forward_precision()
     pkg.ops.backward_gemm_precision(backward)
+    pkg.ops.training_forward_precision(forward)
     try:
         for _ in range(warmup):
             step()
@@ -58,10 +61,11 @@ def nerface_leg(pkg, dev, arch, rays=2048, steps=5, warmup=2, backward="bf16x3")
         dt = (time.perf_counter() - t0) / steps
     finally:
         pkg.ops.backward_gemm_precision(before)
+        pkg.ops.training_forward_precision(fwd_before)
     assert bool(torch.isfinite(loss))
     nc, nf = int(cfg.nerf.train.num_coarse), int(cfg.nerf.train.num_fine)
     return {"arch": arch, "rays": rays, "samples": [rays * nc, rays * (nc + nf)], "ms_per_step": round(dt * 1e3, 3), "steps": steps,
-            "backward": backward, "fused_backward": pkg.ops.fused_backward()}
+            "backward": backward, "forward": forward, "fused_backward": pkg.ops.fused_backward()}
 
 
 def main():
@@ -71,15 +75,24 @@ def main():
     ap.add_argument("--per-layer", action="store_true", help="keep the per-layer backward walk (ops.fused_backward(False))")
     ap.add_argument("--only", default=None, choices=["fp32", "bf16x3", "x3fwd"])
     ap.add_argument("--arch", default="audio", choices=["audio", "nerface", "nerface_static"])
+    ap.add_argument("--repeats", type=int, default=3, help="--only x3fwd with a NeRFace --arch: alternations of the two steps")
     a = ap.parse_args()
     pkg = importlib.import_module("sahs-deformable-nerf_amd")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
     pkg.ops.fused_backward(not a.per_layer)
     out = {"fused_backward": pkg.ops.fused_backward()}
-    if a.arch != "audio":      # (the split-operand training forward is the AudioFaceModel's only: no x3fwd leg)
-        if a.only == "x3fwd":
-            ap.error("--only x3fwd is the AudioFaceModel's")
+    if a.arch != "audio":
+        if a.only == "x3fwd":      # the fp32-forward and the x3-forward step, alternated (same process, same model, default backward)
+            legs = {"fp32fwd": [], "x3fwd": []}
+            for _ in range(a.repeats):
+                for name, fwd in (("fp32fwd", "fp32"), ("x3fwd", "bf16x3")):
+                    legs[name].append(nerface_leg(pkg, dev, a.arch, steps=a.steps, warmup=a.warmup, forward=fwd))
+            for name, runs in legs.items():
+                ms = [r["ms_per_step"] for r in runs]
+                out["train_%s_T2048_%s" % (a.arch, name)] = dict(runs[0], ms_per_step=min(ms), ms_runs=ms)
+            print(json.dumps(out))
+            return
         for mode in ("fp32", "bf16x3"):
             if a.only in (None, mode):
                 out["train_%s_T2048%s" % (a.arch, "" if mode == "fp32" else "_bf16x3")] = nerface_leg(pkg, dev, a.arch, steps=a.steps, warmup=a.warmup,
