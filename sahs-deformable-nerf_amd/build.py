@@ -168,7 +168,8 @@ def build(force=False, verbose=False, defines=(), out=None, check_inflight=True)
             f.write("\n".join(report) + "\n")
         if verbose:
             print("\n".join(report))
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+    # -z defs: a launcher that some table names but no object defines fails here, not at dlopen
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", "-o", LIB] + objs
     subprocess.check_call(cmd)
     return LIB
 

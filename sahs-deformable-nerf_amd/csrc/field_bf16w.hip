@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <utility>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
 #include "bf16_pipe.hpp"
 

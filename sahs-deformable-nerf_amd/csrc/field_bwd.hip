@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
 
 namespace SAHS_NS {
@@ -1811,9 +1812,6 @@ extern "C" long SAHS_SYM(sahs_field_backward_ws_words)(long P) { return P * (256
 // point and the ambient coordinate, (P,8) rows [dx'0 dx'1 dx'2 . dw0 dw1 . .]: the radiance part alone leaves it in xwg_out, the
 // deformation part alone starts from xwg_in, and the whole walk adds xwg_in (if given) at the seam -- that is how the fine pass's
 // gradient reaches the coarse samples' deformation when the forward evaluated the deformation nets once per depth (field_f32.hip MODE).
-extern "C" int SAHS_SYM(sahs_field_backward_split_launch)(const float *flat, const float *frame, int level, int part, long P, const float *actbuf,
-                                                const float *d_raw, const float *xwg_in, float *xwg_out, float *grad_flat, float *grad_cond,
-                                                float *ws, hipStream_t stream);
 extern "C" int SAHS_SYM(sahs_field_backward_launch)(const float *flat, const float *frame, int level, long P, const float *actbuf, const float *d_raw,
                                           float *grad_flat, float *grad_cond, float *ws, hipStream_t stream)
 {
@@ -2086,21 +2084,6 @@ extern "C" int SAHS_SYM(sahs_field_backward_split_launch)(const float *flat, con
 // The NeRFaceModel without deformation nets (SAHS_MODEL 2) has part 3 only, which is its radiance part: no deformation chain, and no seam
 // gradient (nothing upstream of the raw sample point has parameters: its chain stops at dT0, the encodings' backward is not run).
 // ================================================================================================================================
-extern "C" {
-long SAHS_SYM(sahs_bwd_chain_stream_hw)(int part);
-int SAHS_SYM(sahs_bwd_chain_pack_launch)(const float *flat, void *stream_out, int level, int part, hipStream_t stream);
-int SAHS_SYM(sahs_bwd_chain_rad_launch)(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf, float *din_a,
-                                        float *din_b, int num_cu, hipStream_t stream);
-int SAHS_SYM(sahs_bwd_chain_def_launch)(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact, float *g3,
-                                        float *dw4, int num_cu, hipStream_t stream);
-// field_bwd_chain_f32.hip: the same chains in exact fp32 products
-long SAHS_SYM(sahs_bwd_chain_f32_stream_floats)(int part);
-int SAHS_SYM(sahs_bwd_chain_f32_pack_launch)(const float *flat, float *stream_out, int level, int part, hipStream_t stream);
-int SAHS_SYM(sahs_bwd_chain_f32_rad_launch)(const float *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf, float *din_a,
-                                            float *din_b, int num_cu, hipStream_t stream);
-int SAHS_SYM(sahs_bwd_chain_f32_def_launch)(const float *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact, float *g3,
-                                            float *dw4, int num_cu, hipStream_t stream);
-}
 
 namespace {
 constexpr long RAD_PLANES = act::STRIDE - act::XW, DEF_PLANES = act::XW;        // floats per sample of the dZ planes of a part

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <utility>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
 #include "bf16_pipe.hpp"
 #include "bf16x3_pipe.hpp"

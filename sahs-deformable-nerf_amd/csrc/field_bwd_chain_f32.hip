@@ -12,6 +12,7 @@
 // (gemm_dma_kernel<false, false>), same exact products.  Built once per model, with the trunk and the parts of field_bwd_chain.hip's programs.
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
 #include "f32_pipe.hpp"
 

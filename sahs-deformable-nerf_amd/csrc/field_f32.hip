@@ -22,6 +22,7 @@
 // Roofline: MFMA-bound (1.86 MFLOP per sample against ~100 B of HBM traffic).
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
 #include "f32_pipe.hpp"
 
@@ -445,9 +446,6 @@ extern "C" int SAHS_SYM(sahs_field_forward_f32_launch)(const float *packed, cons
 // columns < act::XW + 16: the caller may pass a base such that only that range is backed by memory (sahs_layout_act_part_words).
 // bits (with actbuf): the sign-bit planes of the layers the launch runs (sahs_layout.hpp: sbits; mode 0: [deformation | radiance] planes),
 // (P * sahs_layout_bits_part_words(mode)) 32-bit words, or null
-extern "C" int SAHS_SYM(sahs_field_forward_f32_split_bits_launch)(const float *packed, const float *frame, int level, int mode, long P, int S,
-                                                   const float *rays, int ray_stride, const float *zvals, float *raw, float *xw, int xw_row,
-                                                   int xw_col0, const int *src, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream);
 extern "C" int SAHS_SYM(sahs_field_forward_f32_split_launch)(const float *packed, const float *frame, int level, int mode, long P, int S,
                                                    const float *rays, int ray_stride, const float *zvals, float *raw, float *xw, int xw_row,
                                                    int xw_col0, const int *src, float *actbuf, int num_cu, hipStream_t stream)

@@ -8,6 +8,7 @@
 //    inputs of the six layers that see them into those layers' biases.
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
 
 namespace SAHS_NS {

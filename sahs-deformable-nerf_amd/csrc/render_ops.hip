@@ -5,6 +5,7 @@
 // pdf sum / cumsum -- the same orders the CPU oracle uses) and bandwidth second.
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
 
 namespace sahs {

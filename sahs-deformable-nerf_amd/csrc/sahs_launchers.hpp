@@ -1,0 +1,122 @@
+// sahs_launchers.hpp -- the one declaration of every extern "C" function that one .hip file defines and another calls.
+// Every defining file includes it: a definition whose types drift from its declaration then fails to compile (with C linkage it
+// would still link, and receive garbage arguments at run time).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+extern "C" {
+// render_ops.hip
+int sahs_ray_bundle_launch(int H, int W, float fx, float fy, float cx, float cy, const float *c2w, int ld, float *ro, float *rd,
+                           hipStream_t stream);
+int sahs_stratified_depths_launch(long N, int S, const float *rays, int ray_stride, int lindisp, const float *t_rand, float *z,
+                                  hipStream_t stream);
+int sahs_composite_forward_launch(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
+                                  const float *bg, int white_bkgd, float *rgb_map, float *disp, float *acc_map, float *weights,
+                                  float *depth, float *w_last, int rgb_ld, int sc_ld, hipStream_t stream);
+int sahs_route_xw_grad_launch(long N, int Sc, int nf, const int *src, const float *g_fine, float *g_coarse, float *g_new, hipStream_t stream);
+int sahs_resample_launch(long N, int S, int nf, int from_z, const float *z, const float *weights, const float *u, float *z_samples,
+                         float *z_out, long long *inds, int *src, hipStream_t stream);
+int sahs_ray_uniforms_launch(unsigned long long seed, int stream_id, long ray0, long N, int S, float *out, hipStream_t stream);
+// spade_ops.hip
+long sahs_spade_stats_words(long planes);
+int sahs_spade_modulate_launch(long planes, long hw, const float *x, const float *gamma, const float *beta, float eps, float slope, float *out,
+                               float *stats, hipStream_t stream);
+// train_bwd.hip
+int sahs_composite_backward_launch(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
+                                   const float *bg, int white_bkgd, const float *d_rgb, const float *d_disp, const float *d_acc,
+                                   const float *d_depth, const float *d_wlast, const float *d_weights, float *d_raw, const float *loss_map,
+                                   const float *loss_target, int target_ld, const float *loss_mask, const float *loss_stats,
+                                   const float *loss_gscale, hipStream_t stream);
+int sahs_stage1_loss_forward_launch(long N, const float *map_c, const float *map_f, const float *target, int target_ld, const float *mask,
+                                    const float *class_w, float *stats, hipStream_t stream);
+int sahs_conditioning_backward_launch(const float *flat, const float *audio, const float *grad_cond, float *grad_flat, float *grad_audio,
+                                      hipStream_t stream);
+
+// The sources built once per model (sahs_model.hpp: SAHS_MODEL=0 no suffix, 1 suffix _nf, 2 suffix _ns).  A model build without one of
+// these launchers leaves its name undefined; capi.hip's table holds nullptr there (and the link, -z defs, fails on any other reference).
+#define SAHS_DECLARE_MODEL(sfx)                                                                                                          \
+    /* pack.hip */                                                                                                                       \
+    long sahs_layout_param_count##sfx(void);                                                                                            \
+    long sahs_layout_packed_words_f32##sfx(void);                                                                                       \
+    long sahs_layout_packed_words_bf16##sfx(void);                                                                                      \
+    long sahs_layout_packed_words_bf16x3##sfx(void);                                                                                    \
+    long sahs_layout_frame_words##sfx(void);                                                                                            \
+    long sahs_layout_act_words##sfx(void);                                                                                              \
+    long sahs_layout_executed_macs##sfx(int precision, int part);                                                                       \
+    int sahs_pack_weights_f32_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                       \
+    int sahs_pack_weights_bf16_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                      \
+    int sahs_pack_weights_bf16x3_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                    \
+    int sahs_fold_conditioning_launch##sfx(const float *flat, const float *audio, const float *pose, int pose_ld, float *frame,        \
+                                           hipStream_t stream);                                                                         \
+    /* field_f32.hip */                                                                                                                  \
+    int sahs_layout_act_part_words##sfx(int part);                                                                                      \
+    int sahs_layout_act_part_col0##sfx(int part);                                                                                       \
+    int sahs_layout_bits_part_words##sfx(int part);                                                                                     \
+    int sahs_field_forward_f32_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,       \
+                                           int ray_stride, const float *zvals, float *raw, float *dbg, float *actbuf, int num_cu,       \
+                                           hipStream_t stream);                                                                         \
+    int sahs_field_forward_f32_split_launch##sfx(const float *packed, const float *frame, int level, int mode, long P, int S,          \
+                                                 const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,          \
+                                                 int xw_row, int xw_col0, const int *src, float *actbuf, int num_cu,                    \
+                                                 hipStream_t stream);                                                                   \
+    int sahs_field_forward_f32_split_bits_launch##sfx(const float *packed, const float *frame, int level, int mode, long P, int S,     \
+                                                      const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,     \
+                                                      int xw_row, int xw_col0, const int *src, float *actbuf, uint32_t *bits,           \
+                                                      int num_cu, hipStream_t stream);                                                  \
+    /* field_bf16w.hip */                                                                                                                \
+    int sahs_bf16w_exact_leaky_state##sfx(int set);                                                                                     \
+    int sahs_field_forward_bf16w_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,     \
+                                             int ray_stride, const float *zvals, float *raw, float *dbg, int num_cu, hipStream_t stream); \
+    int sahs_field_forward_bf16w_split_launch##sfx(const float *packed, const float *frame, int level, int mode, long P, int S,        \
+                                                   const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,        \
+                                                   int xw_row, int xw_col0, const int *src, int num_cu, hipStream_t stream);            \
+    /* field_bf16x3.hip */                                                                                                               \
+    int sahs_field_deform_bf16x3_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,     \
+                                             int ray_stride, const float *zvals, float *xw, int xw_row, int xw_col0, int num_cu,        \
+                                             hipStream_t stream);                                                                       \
+    int sahs_field_deform_bf16x3_save_launch##sfx(const float *packed, const float *frame, int level, long P, int S,                  \
+                                                  const float *rays, int ray_stride, const float *zvals, float *xw, int xw_row,         \
+                                                  int xw_col0, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream);          \
+    int sahs_field_radiance_bf16x3_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,   \
+                                               int ray_stride, float *raw, const float *xw, int xw_row, const int *src, int num_cu,     \
+                                               hipStream_t stream);                                                                     \
+    int sahs_field_radiance_bf16x3_save_launch##sfx(const float *packed, const float *frame, int level, long P, int S,                \
+                                                    const float *rays, int ray_stride, float *raw, const float *xw, int xw_row,         \
+                                                    const int *src, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream);     \
+    int sahs_field_forward_bf16x3_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,    \
+                                              int ray_stride, const float *zvals, float *raw, int num_cu, hipStream_t stream);          \
+    int sahs_field_forward_bf16x3_save_launch##sfx(const float *packed, const float *frame, int level, long P, int S,                  \
+                                                   const float *rays, int ray_stride, const float *zvals, float *raw, float *actbuf,    \
+                                                   uint32_t *bits, int num_cu, hipStream_t stream);                                     \
+    /* field_bwd.hip */                                                                                                                  \
+    int sahs_bwd_gemm_precision_state##sfx(int set);                                                                                    \
+    long sahs_field_backward_ws_words##sfx(long P);                                                                                     \
+    int sahs_field_backward_launch##sfx(const float *flat, const float *frame, int level, long P, const float *actbuf,                  \
+                                        const float *d_raw, float *grad_flat, float *grad_cond, float *ws, hipStream_t stream);         \
+    int sahs_field_backward_split_launch##sfx(const float *flat, const float *frame, int level, int part, long P, const float *actbuf,  \
+                                              const float *d_raw, const float *xwg_in, float *xwg_out, float *grad_flat,                \
+                                              float *grad_cond, float *ws, hipStream_t stream);                                         \
+    long sahs_field_backward_fused_ws_words##sfx(int part, long P);                                                                     \
+    int sahs_field_backward_fused_launch##sfx(const float *flat, const float *frame, int level, int part, long P, const float *actbuf,  \
+                                              const uint32_t *bits, const float *d_raw, const float *xwg_in, float *xwg_out,            \
+                                              float *grad_flat, float *grad_cond, float *ws, int num_cu, hipStream_t stream);           \
+    /* field_bwd_chain.hip: the fused walk's data-gradient chains (split bf16 operands) */                                              \
+    long sahs_bwd_chain_stream_hw##sfx(int part);                                                                                       \
+    int sahs_bwd_chain_pack_launch##sfx(const float *flat, void *stream_out, int level, int part, hipStream_t stream);                 \
+    int sahs_bwd_chain_rad_launch##sfx(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact,             \
+                                       float *dgridf, float *din_a, float *din_b, int num_cu, hipStream_t stream);                      \
+    int sahs_bwd_chain_def_launch##sfx(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits,       \
+                                       float *dact, float *g3, float *dw4, int num_cu, hipStream_t stream);                             \
+    /* field_bwd_chain_f32.hip: the same chains in exact fp32 products */                                                               \
+    long sahs_bwd_chain_f32_stream_floats##sfx(int part);                                                                               \
+    int sahs_bwd_chain_f32_pack_launch##sfx(const float *flat, float *stream_out, int level, int part, hipStream_t stream);             \
+    int sahs_bwd_chain_f32_rad_launch##sfx(const float *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact,         \
+                                           float *dgridf, float *din_a, float *din_b, int num_cu, hipStream_t stream);                  \
+    int sahs_bwd_chain_f32_def_launch##sfx(const float *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits,   \
+                                           float *dact, float *g3, float *dw4, int num_cu, hipStream_t stream);
+SAHS_DECLARE_MODEL()
+SAHS_DECLARE_MODEL(_nf)
+SAHS_DECLARE_MODEL(_ns)
+#undef SAHS_DECLARE_MODEL
+}

@@ -8,6 +8,7 @@
 // stay on MIOpen through PyTorch (hand-written convolutions would buy nothing on this path).
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 
 namespace sahs {
 

@@ -1,6 +1,7 @@
 // train_bwd.hip -- backward of the compositing stage and of the per-frame conditioning (AudioNet + fold).
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
+#include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
 
 namespace sahs {

@@ -382,11 +382,9 @@ def field_forward_save(packed, frame, level, rays, z, arch="audio", bits=None, p
         bits = _req(bits, "bits", torch.int32)
         if tuple(bits.shape) != (N * S, int(_fn("bits_words_part", arch)[0](FIELD_ALL))):
             raise _lib.SahsError("field_forward_save: bits must come from alloc_sign_bits(N * S, FIELD_ALL, arch, device)")
-        f, name = _fn("field_forward_save_bits_x3" if x3 else "field_forward_save_bits", arch)
-        check(f(_p(packed), _p(frame), int(level), N, S, _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(act), _p(bits), _stream()), name)
-        return raw, act
-    f, name = _fn("field_forward_save", arch)
-    check(f(_p(packed), _p(frame), int(level), N, S, _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(act), _stream()), name)
+    f, name = _fn("field_forward_save" + ("" if bits is None else "_bits_x3" if x3 else "_bits"), arch)
+    out = [_p(act)] if bits is None else [_p(act), _p(bits)]
+    check(f(_p(packed), _p(frame), int(level), N, S, _p(rays), int(rays.shape[1]), _p(z), _p(raw), *out, _stream()), name)
     return raw, act
 
 
@@ -430,24 +428,19 @@ def field_forward_split_save(packed, frame, level, mode, rays, xw, z=None, src=N
         radiance = int(mode) == FIELD_RADIANCE      # the radiance arrays / planes are the tail of the whole-network tables
         act_ptr = ctypes.c_void_p(act.data_ptr() + (4 * (int(words(FIELD_ALL)) - int(words(FIELD_RADIANCE))) * N * S if radiance else 0))
         bits_ptr = ctypes.c_void_p(bits.data_ptr() + (4 * int(bwords(FIELD_DEFORM)) * N * S if radiance else 0))
-        f, name = _fn("field_forward_split_save_bits_x3" if int(precision) == SAHS_BF16X3 else "field_forward_split_save_bits", arch)
-        check(f(_p(packed), _p(frame), int(level), int(mode), N, int(S), _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(xw), int(xw.shape[1]), int(xw_col0),
-                _p(src), act_ptr, bits_ptr, _stream()), name)
-        return raw, act
-    act = torch.empty(N * S, words(int(mode)), dtype=torch.float32, device=rays.device)
-    if bits is not None:
-        bits = _req(bits, "bits", torch.int32)
-        if tuple(bits.shape) != (N * S, int(bwords(int(mode)))):
-            raise _lib.SahsError("field_forward_split_save: bits must come from alloc_sign_bits(N * S, mode, arch, device)")
-        f, name = _fn("field_forward_split_save_bits_x3" if int(precision) == SAHS_BF16X3 else "field_forward_split_save_bits", arch)
-        check(f(_p(packed), _p(frame), int(level), int(mode), N, int(S), _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(xw), int(xw.shape[1]), int(xw_col0),
-                _p(src), _p(act), _p(bits), _stream()), name)
-        return raw, act
-    if int(precision) != SAHS_F32:
-        raise _lib.SahsError("field_forward_split_save: a saving forward at a precision other than fp32 needs the sign bits (bits=alloc_sign_bits(...))")
-    f, name = _fn("field_forward_split_save", arch)
+    else:
+        act = torch.empty(N * S, words(int(mode)), dtype=torch.float32, device=rays.device)
+        if bits is not None:
+            bits = _req(bits, "bits", torch.int32)
+            if tuple(bits.shape) != (N * S, int(bwords(int(mode)))):
+                raise _lib.SahsError("field_forward_split_save: bits must come from alloc_sign_bits(N * S, mode, arch, device)")
+        elif int(precision) != SAHS_F32:
+            raise _lib.SahsError("field_forward_split_save: a saving forward at a precision other than fp32 needs the sign bits (bits=alloc_sign_bits(...))")
+        act_ptr, bits_ptr = _p(act), _p(bits)
+    f, name = _fn("field_forward_split_save" + ("" if bits is None else "_bits_x3" if int(precision) == SAHS_BF16X3 else "_bits"), arch)
+    out = [act_ptr] if bits is None else [act_ptr, bits_ptr]
     check(f(_p(packed), _p(frame), int(level), int(mode), N, int(S), _p(rays), int(rays.shape[1]), _p(z), _p(raw), _p(xw), int(xw.shape[1]), int(xw_col0),
-            _p(src), _p(act), _stream()), name)
+            _p(src), *out, _stream()), name)
     return raw, act
 
 
