@@ -312,6 +312,23 @@ int sahs_model_render_rays_rows(int model, const void *packed, const float *fram
                                 const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f, float *raw,
                                 float *weights, float *rows, int row_ld, float *xw, int32_t *src, float *z_new, void *stream);
 
+/* ---- optimiser step (the training step's "Adam/LR schedule") ----
+ * torch.optim.Adam with weight_decay = 0, amsgrad = False, maximize = False -- what the reference builds
+ * (train_stage_rays_auto.py:201-209: getattr(torch.optim, "Adam")(params, lr=cfg.optimizer.lr)) -- as ONE launch over the n contiguous
+ * fp32 values of the canonical flat buffer; params, exp_avg, exp_avg_sq are updated in place:
+ *     g = grad * grad_scale                                (1 on one GPU, 1 / world after a summed all-reduce)
+ *     exp_avg    += (g - exp_avg) * (1 - beta1)
+ *     exp_avg_sq  = exp_avg_sq * beta2 + (1 - beta2) * g * g
+ *     params     -= lr / (1 - beta1^step) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps)
+ * step: the 1-based count of this update; both bias corrections are formed from it in double on the host.  lr, beta1, beta2 and eps are
+ * read as the shortest decimal that rounds to the float given (0.999f means 0.999), so the scalars are the ones torch forms from Python
+ * floats.  sqrt and the divisions are correctly rounded.  Buffers need 4-byte alignment only (16-byte accesses where all four share an
+ * alignment, element by element otherwise).  Invalid: a null pointer, n < 0, step < 1, lr or eps not finite and positive, a beta outside
+ * [0, 1), params / exp_avg / exp_avg_sq overlapping.  n == 0 succeeds without a launch.  A training step on this ABI is
+ * sahs_model_field_backward* -> sahs_adam_step -> sahs_model_pack_weights. */
+int sahs_adam_step(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1, float beta2,
+                   float eps, long step, float grad_scale, void *stream);
+
 /* ---- Stage-II refiner building block ----
  * The elementwise core of SPADELayer.forward followed by its SPADEBlock's LeakyReLU (nerf/_init_spade.py:130-139, :262-279):
  *   out = lrelu_slope( InstanceNorm2d(x; eps, biased variance, no affine) * (1 + gamma) + beta )

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsahs_nerf.so")
-SOURCES = ["capi.hip", "pack.hip", "render_ops.hip", "spade_ops.hip", "field_f32.hip", "field_bf16w.hip", "field_bf16x3.hip", "field_bwd.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip", "train_bwd.hip"]
+SOURCES = ["capi.hip", "pack.hip", "render_ops.hip", "spade_ops.hip", "optim.hip", "field_f32.hip", "field_bf16w.hip", "field_bf16x3.hip", "field_bwd.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip", "train_bwd.hip"]
 # sources built again for the NeRFaceModel architectures (csrc/sahs_model.hpp: -DSAHS_MODEL=1 / 2, symbols suffixed _nf / _ns)
 MODEL_SOURCES = ["pack.hip", "field_f32.hip", "field_bwd.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip"]
 X3_SOURCES = ["field_bf16x3.hip"]      # NeRFaceModels: the split-operand kernels (SAHS_BF16X3; with deformation nets also the mixed precision's)
@@ -29,7 +29,7 @@ FIELD_FLAGS = ["-fno-honor-nans", "-mno-amdgpu-ieee"]
 NO_SCRATCH = {"gemm_dma_kernel": 0, "_ZN4sahs24field_forward_f32_kernelILb0E": 0, "field_forward_bf16w_kernel": 0,
               "field_radiance_bf16x3_kernel": 0, "field_deform_bf16x3_kernel": 0, "gemm_tn_split_kernel": 0, "gemm_tn_jobs_kernel": 0,
               "field_backward_chain_rad_kernel": 0, "field_backward_chain_def_kernel": 0, "_ZN4sahs24field_forward_f32_kernelILb1E": 96,
-              "gemm_tn_jobs_f32_kernel": 0, "gemm_tn_jobs256_f32_kernel": 0,
+              "gemm_tn_jobs_f32_kernel": 0, "gemm_tn_jobs256_f32_kernel": 0, "adam_step_kernel": 0,      # (a streaming kernel: nothing to spill)
               "field_backward_chain_rad_f32_kernel": 0, "field_backward_chain_def_f32_kernel": 0,
               # (the names above match every model's build; the NeRFaceModel instances of the fused walk's chains, spelled out)
               "_ZN7sahs_nf3bwc31field_backward_chain_rad_kernel": 0, "_ZN7sahs_nf3bwc31field_backward_chain_def_kernel": 0,

@@ -1,8 +1,10 @@
 // capi.hip -- the extern "C" boundary declared in include/sahs_nerf.h: argument validation,
 // error text, and the chained predict_and_render_radiance launch sequence.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <atomic>
 #include <vector>
@@ -220,6 +222,39 @@ int sahs_route_xw_grad(long N, int Sc, int nf, const int32_t *src, const float *
             "sahs_route_xw_grad");
     int e = sahs_route_xw_grad_launch(N, Sc, nf, src, g_fine, g_coarse, g_new, (hipStream_t)stream);
     return e ? hip_fail("sahs_route_xw_grad", e) : 0;
+}
+
+// A float argument is taken as the SHORTEST decimal that rounds to it, read back in double: a caller writes beta2 = 0.999f and means 0.999
+// (torch forms 1 - beta2 = 1.0000000000000009e-3 in double), while the float's own value gives 1 - 0.99900001287 = 9.99987e-4 -- 1.3e-5 relative off
+// in every second-moment update, a hundred times the rounding error of the fp32 update itself.
+static double decimal_double(float x)
+{
+    char buf[32];
+    for (int digits = 1; digits <= 9; ++digits) {
+        snprintf(buf, sizeof(buf), "%.*g", digits, (double)x);
+        if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
+    }
+    return (double)x;
+}
+
+int sahs_adam_step(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1, float beta2, float eps,
+                   long step, float grad_scale, void *stream)
+{
+    if (n == 0) return 0;
+    REQUIRE(params && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, "sahs_adam_step");
+    REQUIRE(std::isfinite(lr) && lr > 0.0f && std::isfinite(eps) && eps > 0.0f && std::isfinite(grad_scale), "sahs_adam_step(lr > 0, eps > 0, finite)");
+    REQUIRE(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f, "sahs_adam_step(0 <= beta < 1)");
+    const uintptr_t p = reinterpret_cast<uintptr_t>(params), g = reinterpret_cast<uintptr_t>(grad), m = reinterpret_cast<uintptr_t>(exp_avg),
+                    v = reinterpret_cast<uintptr_t>(exp_avg_sq), bytes = (uintptr_t)n * sizeof(float);
+    REQUIRE(((p | g | m | v) & 3u) == 0, "sahs_adam_step(4-byte aligned buffers)");
+    auto overlap = [bytes](uintptr_t a, uintptr_t b) { return a < b + bytes && b < a + bytes; };
+    REQUIRE(!overlap(p, m) && !overlap(p, v) && !overlap(m, v), "sahs_adam_step(params, exp_avg, exp_avg_sq must not overlap)");
+    const double b1 = decimal_double(beta1), b2 = decimal_double(beta2);
+    const double bc1 = 1.0 - std::pow(b1, (double)step), bc2 = 1.0 - std::pow(b2, (double)step);
+    int e = sahs_adam_step_launch(params, grad, exp_avg, exp_avg_sq, n, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2),
+                                  (float)(decimal_double(lr) / bc1), (float)std::sqrt(bc2), (float)decimal_double(eps), grad_scale,
+                                  (hipStream_t)stream);
+    return e ? hip_fail("sahs_adam_step", e) : 0;
 }
 
 long sahs_spade_modulate_workspace_words(long planes) { return planes > 0 ? sahs_spade_stats_words(planes) : 0; }

@@ -119,6 +119,17 @@ def all_reduce_gradients(params, group=None, average=True):
         o += n
 
 
+def all_reduce_flat_gradient(flat_grad, group=None):
+    """The same reduction for a model whose gradients ARE one flat buffer (models.flatten_parameters_): one in-place summed all-reduce,
+    no concatenation and no copy back.  Returns the factor that turns the sum into the average, 1 / world, for the optimiser kernel to
+    apply as it reads the gradient (ops.adam_step: grad_scale)."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    if world == 1:
+        return 1.0
+    dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=group)
+    return 1.0 / world
+
+
 def shard_batch(num_rays, group=None):
     """This rank's slice of a training batch's ray list (every rank draws the same batch from a shared seed)."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1

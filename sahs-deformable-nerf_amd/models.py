@@ -85,9 +85,29 @@ def _check_cfg(cfg, arch):
                                   "Mismatches (got, want): %r" % (bad,))
 
 
+class _FlatLink(torch.autograd.Function):
+    """The autograd link of a flattened model's parameter buffer: forward hands out the buffer (an alias, no copy), backward adds the flat
+    gradient that RenderRaysFn.backward produces into the model's flat gradient buffer -- one add, whatever the number of parameters.
+    ``anchor`` is a leaf that only makes autograd record the node; it receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, anchor, model):
+        ctx.model = model
+        return model._flat.detach()
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.model._flat_grad.add_(g)
+        return None, None
+
+
 class _FieldModel(nn.Module):
     """Shared plumbing: parameters in the reference's state_dict layout, packed lazily for the HIP field kernel."""
     arch = "audio"
+    _flat = None          # flatten_parameters_(): the ONE contiguous fp32 buffer every parameter is a view of (canonical order) ...
+    _flat_grad = None     # ... and the one every .grad is a view of
+    _flat_params = _flat_anchor = None
+    _flat_epoch = 0       # bumped by whatever writes the buffer through a raw pointer (the optimiser kernel: training.FlatAdam.step)
 
     def _build(self, cfg, precision):
         _check_cfg(cfg, self.arch)
@@ -108,16 +128,129 @@ class _FieldModel(nn.Module):
         assert list(self.state_dict().keys()) == keys, "state_dict layout drifted from the reference's"
         self._cache = {}
 
+    # ---- flat parameter storage (opt-in: training.FlatAdam) ----
+    def flatten_parameters_(self):
+        """Move every parameter into ONE contiguous fp32 buffer (weights.canonical_spec order = parameters() order) and every .grad into
+        one flat gradient buffer; the nn.Parameters stay, as views at their canonical offsets, so state_dict / load_state_dict / checkpoints
+        are unchanged.  The HIP backward already produces one flat gradient and the optimiser kernel (ops.adam_step) updates one flat
+        buffer: after this call flat_params() is that buffer (no torch.cat), flat_params(differentiable=True) routes the backward's gradient
+        into the flat gradient buffer with one add, and packed() is fed from the buffer.  Every parameter must be trainable and fp32 (the
+        reference trains all of them).  Use with training.FlatAdam; an optimiser that drops .grad (zero_grad(set_to_none=True) of
+        torch.optim) breaks the views, which flat_params(differentiable=True) reports.  unflatten_parameters_() undoes it."""
+        if self._flat is not None:
+            return self
+        named = list(self.named_parameters())
+        assert [k for k, _ in named] == [k for k, _ in W.canonical_spec(self.arch)]
+        bad = [k for k, p in named if not p.requires_grad or p.dtype != torch.float32]
+        if bad:
+            raise RuntimeError("flatten_parameters_: every parameter must be trainable fp32; not so: %s" % ", ".join(bad[:4]))
+        params = [p for _, p in named]
+        if len({p.device for p in params}) != 1:
+            raise RuntimeError("flatten_parameters_: the parameters live on several devices")
+        n = sum(p.numel() for p in params)
+        flat = torch.empty(n, dtype=torch.float32, device=params[0].device)
+        grad = torch.zeros(n, dtype=torch.float32, device=params[0].device)
+        off = 0
+        with torch.no_grad():
+            for p in params:
+                k = p.numel()
+                flat[off:off + k].copy_(p.detach().reshape(-1))
+                if p.grad is not None:
+                    grad[off:off + k].copy_(p.grad.reshape(-1))
+                p.data = flat[off:off + k].view(p.shape)
+                p.grad = grad[off:off + k].view(p.shape)
+                off += k
+        self._flat, self._flat_grad, self._flat_params = flat, grad, params
+        self._flat_anchor = torch.zeros((), requires_grad=True)
+        self._cache.clear()
+        return self
+
+    def unflatten_parameters_(self):
+        """Leave flat mode: every parameter (and gradient) gets storage of its own again, values unchanged."""
+        if self._flat is None:
+            return self
+        with torch.no_grad():
+            for p in self._flat_params:
+                g = p.grad
+                p.data = p.detach().clone()
+                p.grad = None if g is None else g.clone()
+        self._flat = self._flat_grad = self._flat_params = self._flat_anchor = None
+        self._cache.clear()
+        return self
+
+    def _check_flat_views(self):
+        """Every parameter and gradient still aliases its buffer at its canonical offset (after anything that may rebind them)."""
+        off = 0
+        live = list(self.parameters())
+        for i, p in enumerate(self._flat_params):
+            if (i >= len(live) or live[i] is not p or p.data_ptr() != self._flat.data_ptr() + 4 * off or not p.is_contiguous() or p.grad is None
+                    or p.grad.data_ptr() != self._flat_grad.data_ptr() + 4 * off):
+                raise RuntimeError("a parameter (or its .grad) of this flattened model no longer aliases the flat buffer -- it was rebound "
+                                   "(load_state_dict(assign=True), an optimiser's zero_grad(set_to_none=True), p.data = ...); call "
+                                   "unflatten_parameters_() before such a change, flatten_parameters_() after it")
+            off += p.numel()
+
+    def _apply(self, fn, recurse=True):
+        """.to() / .cuda() / .float() ...: a flattened model keeps its layout (the buffers move, the views are rebuilt); a conversion away from
+        fp32 is refused, because parameters that no longer alias the buffer would train on stale packed weights."""
+        if self._flat is None:
+            return super()._apply(fn, recurse)
+        if fn(self._flat[:0]).dtype != torch.float32:
+            raise RuntimeError("a flattened model is fp32: call unflatten_parameters_() before converting it to another dtype")
+        self.unflatten_parameters_()
+        super()._apply(fn, recurse)
+        return self.flatten_parameters_()
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy clones every Parameter into storage of its own: the copy of a flattened model is flattened again (gradients zero)."""
+        import copy
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        state = dict(self.__dict__)
+        if self._flat is not None:
+            for k in ("_flat", "_flat_grad", "_flat_params", "_flat_anchor"):
+                state.pop(k, None)
+            state["_cache"] = {}
+        new.__dict__.update(copy.deepcopy(state, memo))
+        if self._flat is not None:
+            new.flatten_parameters_()
+        return new
+
+    def zero_grad(self, set_to_none=True):
+        if self._flat is None:
+            return super().zero_grad(set_to_none)
+        self._flat_grad.zero_()      # one memset; the .grad views stay
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        if self._flat is not None:      # (copy_ into the views: written through, and seen by packed() through the version counters)
+            self._check_flat_views()
+        return out
+
     # ---- weight plumbing ----
     def flat_params(self, differentiable=False):
         """Canonical flat buffer (state_dict order).  differentiable=True keeps the autograd link to the parameters, so a
-        gradient w.r.t. the flat buffer (RenderRaysFn.backward) is scattered back to every nn.Parameter by torch.cat's backward."""
+        gradient w.r.t. the flat buffer (RenderRaysFn.backward) is scattered back to every nn.Parameter by torch.cat's backward.
+        Flattened model: the buffer itself; differentiable=True: an alias whose backward adds into the flat gradient buffer."""
+        if self._flat is not None:
+            if not differentiable:
+                return self._flat
+            if self._flat_params[0].grad is None or self._flat_params[-1].grad is None:
+                self._check_flat_views()
+            return _FlatLink.apply(self._flat_anchor, self)
         sd = dict(self.named_parameters())
         flat = torch.cat([sd[k].reshape(-1) for k, _ in W.canonical_spec(self.arch)]).float().contiguous()
         return flat if differentiable else flat.detach()
 
     def load_flat(self, flat):
         off = 0
+        if self._flat is not None:
+            src = torch.as_tensor(flat).reshape(-1)
+            if src.numel() != self._flat.numel():
+                raise ValueError("load_flat: %d values, the model has %d" % (src.numel(), self._flat.numel()))
+            with torch.no_grad():
+                self._flat.copy_(src)
+            return self
         with torch.no_grad():
             sd = dict(self.named_parameters())
             for k, shape in W.canonical_spec(self.arch):
@@ -129,6 +262,16 @@ class _FieldModel(nn.Module):
     def packed(self, precision=None):
         """Packed weight stream for the HIP field kernel; re-packed when any parameter changed."""
         precision = self.precision if precision is None else precision
+        if self._flat is not None:
+            # The optimiser kernel writes the buffer through a raw pointer, which no version counter sees: it bumps _flat_epoch instead
+            # (training.FlatAdam.step).  torch's own writes are counted: into the buffer (load_flat) by its counter, into one parameter
+            # (load_state_dict, an in-place edit under no_grad) by that parameter's -- counters only grow, so their sum changes with any.
+            key = (precision, self._flat_epoch, self._flat._version, sum(p._version for p in self._flat_params), self._flat.data_ptr())
+            hit = self._cache.get(("packed", precision))
+            if hit is None or hit[0] != key:
+                hit = (key, ops.pack_weights(self._flat, precision, arch=self.arch), self._flat)
+                self._cache["packed", precision] = hit
+            return hit[1], hit[2]
         params = list(self.parameters())
         key = (precision, params[0].device, tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
         hit = self._cache.get(("packed", precision))      # (one entry per precision: a training step on the split-operand forward holds two)

@@ -330,6 +330,19 @@ def spade_modulate(x, gamma, beta, eps=1e-5, slope=1.0):
     return out
 
 
+def adam_step(params, grad, exp_avg, exp_avg_sq, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, grad_scale=1.0):
+    """One torch.optim.Adam update (weight_decay 0, no amsgrad) of n contiguous fp32 values, in place on params / exp_avg / exp_avg_sq, as one
+    HIP launch (include/sahs_nerf.h: sahs_adam_step).  step: the 1-based count of this update; grad is read as grad * grad_scale."""
+    for t, name in ((params, "params"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if _req(t, name) is not t:      # (updated in place: a contiguous copy would take the update with it)
+            raise _lib.SahsError("adam_step: %s must be contiguous" % name)
+        if t.numel() != params.numel():
+            raise _lib.SahsError("adam_step: %s has %d values, params has %d" % (name, t.numel(), params.numel()))
+    check(_lib.lib().sahs_adam_step(_p(params), _p(grad), _p(exp_avg), _p(exp_avg_sq), params.numel(), float(lr), float(beta1), float(beta2),
+                                    float(eps), int(step), float(grad_scale), _stream()), "sahs_adam_step")
+    return params
+
+
 class LaunchProbe:
     """HIP events around every FIELD-kernel launch the library makes on this thread while the block is open (include/sahs_nerf.h:
     sahs_probe_*), recorded on the launch stream: per-kernel times of the product's own call chain (bench.py's roofline).

@@ -99,7 +99,10 @@ def train_step(model, optimizer, cfg, step, image, mask, pose, intrinsics, audio
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     if dist.is_initialized() and dist.get_world_size(group) > 1:
-        D.all_reduce_gradients(model.parameters(), group)
+        if getattr(optimizer, "flat_grad", None) is not None:      # FlatAdam: the gradients are one buffer, averaged as the kernel reads them
+            optimizer.grad_scale = D.all_reduce_flat_gradient(optimizer.flat_grad, group)
+        else:
+            D.all_reduce_gradients(model.parameters(), group)
         stats = torch.cat([new_prob, loss.detach().reshape(1), fine_mse.detach().reshape(1)])
         dist.all_reduce(stats, group=group)
         stats /= dist.get_world_size(group)
@@ -108,6 +111,107 @@ def train_step(model, optimizer, cfg, step, image, mask, pose, intrinsics, audio
     for param_group in optimizer.param_groups:
         param_group["lr"] = learning_rate(cfg, step)
     return dict(loss=float(loss.detach()), psnr=mse2psnr(float(fine_mse.detach())), sample_prob=new_prob)
+
+
+class FlatAdam:
+    """torch.optim.Adam (weight_decay 0, no amsgrad: what the reference builds, train_stage_rays_auto.py:201-209) for a model whose
+    parameters are one flat buffer (model.flatten_parameters_()): step() is ONE HIP launch over that buffer (ops.adam_step) instead of
+    torch's per-tensor kernels, and zero_grad() one memset of the flat gradient buffer.  Drop-in where train_step and the checkpoint
+    functions use an optimiser: param_groups[0]["lr"] is read at every step, and state_dict() / load_state_dict() speak
+    torch.optim.Adam's format (per-parameter step / exp_avg / exp_avg_sq), so a checkpoint written with either loads into the other."""
+
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8):
+        if getattr(model, "_flat", None) is None:
+            raise ValueError("FlatAdam needs a flattened model: call model.flatten_parameters_() first")
+        self.model = model
+        params = list(model._flat_params)
+        if any(not p.requires_grad for p in params):
+            raise ValueError("FlatAdam trains every parameter of the model")
+        # the param-group keys (and their defaults) of the installed torch
+        group = torch.optim.Adam([torch.zeros(1)], lr=lr, betas=betas, eps=eps).state_dict()["param_groups"][0]
+        self.param_groups = [dict(group, params=params)]
+        self.exp_avg = torch.zeros_like(model._flat)
+        self.exp_avg_sq = torch.zeros_like(model._flat)
+        self._step = 0
+        self.grad_scale = 1.0      # train_step sets 1 / world after its summed all-reduce of flat_grad
+
+    @property
+    def flat_grad(self):
+        return self.model._flat_grad
+
+    def _group(self):
+        if len(self.param_groups) != 1:
+            raise NotImplementedError("FlatAdam has one param group (the reference's train_background groups are not covered)")
+        g = self.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+            raise NotImplementedError("FlatAdam is plain Adam: weight_decay = 0, amsgrad = False, maximize = False")
+        return g
+
+    def zero_grad(self, set_to_none=True):
+        """One memset; the parameters' .grad stay views of the flat gradient buffer whatever set_to_none says."""
+        self.model._flat_grad.zero_()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from . import ops
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g, m = self._group(), self.model
+        if m._flat is None or m._flat.numel() != self.exp_avg.numel() or m._flat.device != self.exp_avg.device:
+            raise RuntimeError("the model left flat mode or moved to another device since this optimiser was built")
+        self._step += 1
+        ops.adam_step(m._flat, m._flat_grad, self.exp_avg, self.exp_avg_sq, lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"],
+                      step=self._step, grad_scale=self.grad_scale)
+        m._flat_epoch += 1      # the kernel wrote the parameters through a raw pointer: model.packed() must re-pack
+        return loss
+
+    def _views(self, flat):
+        out, off = [], 0
+        for p in self.model._flat_params:
+            out.append(flat[off:off + p.numel()].view(p.shape))
+            off += p.numel()
+        return out
+
+    def state_dict(self):
+        g = self._group()
+        n = len(g["params"])
+        state = {}
+        if self._step > 0:
+            for i, (a, b) in enumerate(zip(self._views(self.exp_avg), self._views(self.exp_avg_sq))):
+                state[i] = {"step": torch.tensor(float(self._step)), "exp_avg": a, "exp_avg_sq": b}
+        return {"state": state, "param_groups": [dict({k: v for k, v in g.items() if k != "params"}, params=list(range(n)))]}
+
+    def load_state_dict(self, state_dict):
+        groups = state_dict["param_groups"]
+        if len(groups) != 1:
+            raise NotImplementedError("FlatAdam has one param group")
+        params = self.param_groups[0]["params"]
+        if len(groups[0]["params"]) != len(params):
+            raise ValueError("the optimiser state covers %d parameters, the model has %d" % (len(groups[0]["params"]), len(params)))
+        state = state_dict["state"]
+        steps = {int(s["step"]) for s in state.values()}
+        if state and (len(state) != len(params) or len(steps) != 1):
+            raise ValueError("FlatAdam keeps one step count for all parameters: the state must cover every parameter at the same step")
+        old = self.param_groups
+        self.param_groups = [dict({k: (tuple(v) if k == "betas" else v) for k, v in groups[0].items() if k != "params"}, params=params)]
+        try:
+            self._group()
+        except NotImplementedError:
+            self.param_groups = old
+            raise
+        with torch.no_grad():
+            if not state:
+                self._step = 0
+                self.exp_avg.zero_()
+                self.exp_avg_sq.zero_()
+                return
+            for idx, a, b in zip(groups[0]["params"], self._views(self.exp_avg), self._views(self.exp_avg_sq)):
+                s = state[idx]
+                a.copy_(s["exp_avg"])
+                b.copy_(s["exp_avg_sq"])
+            self._step = steps.pop()
 
 
 def save_checkpoint(path, step, model, optimizer, loss, i_batch=0, background=None, latent_codes=None, pose_c=None, sample_prob=None):
