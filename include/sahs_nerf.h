@@ -217,7 +217,9 @@ long sahs_model_executed_macs_part(int model, int precision, int part);
 int sahs_composite_forward_rows(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
                                 const float *bg, int white_background, float *weights, float *rows, int row_ld, int fine_pass, void *stream);
 /* z_vals_mid + sample_pdf_2 + cat + sort as sahs_resample, also returning the merge permutation: src (N,S+nf) int32, position s of the
- * sorted row holds element src[s] of cat(z, z_samples) (train_utils.py:166; equal values keep that order). */
+ * sorted row holds element src[s] of cat(z, z_samples) (train_utils.py:166; equal values keep that order).
+ * GUARANTEE: src[ray] is ALWAYS a permutation of 0..S+nf-1 and every slot of z_out and src is written, whatever the inputs hold: the
+ * order is torch.sort's total order -- a NaN (non-finite weights make a ray's new samples NaN) follows every number, NaNs in index order. */
 int sahs_resample_merge(long N, int S, int nf, const float *z, const float *weights, const float *u, float *z_samples, float *z_out,
                         int32_t *src, void *stream);
 

@@ -361,6 +361,10 @@ __global__ void __launch_bounds__(RS_WAVES * 64) resample_kernel(long N, int S, 
         // rank sort of the S+nf values (ascending; equal values keep index order).  The depths z of a ray arrive sorted (stratified bins), so
         // rank(z_a) = a + #{samples < z_a} and rank(sample_j) = #{z <= sample_j} + #{samples before it in the stable order}: half the
         // comparisons, four values per LDS read; rows that are not sorted (the seam accepts any z) take the general count.
+        // The order is TOTAL, torch.sort's: a NaN (a diverged ray's weights make every new sample NaN) follows every number, NaNs keep index
+        // order.  Every comparison with a NaN is false, so a number's count above already leaves the NaNs behind it; a NaN counts for itself
+        // (all numbers + the NaNs before it).  Hence every slot of z_out / src is written exactly once and src is ALWAYS a permutation of
+        // 0..S+nf-1 -- the next launch gathers xw[ray, src] unchecked.  (A sorted row holds no NaN depth: each z sits in a comparison that held.)
         const int M = from_z ? S + nf : 0;
         bool sorted = true;
         for (int i = lane; i + 1 < S && M > 0; i += 64) sorted = sorted && (val[i] <= val[i + 1]);
@@ -374,6 +378,13 @@ __global__ void __launch_bounds__(RS_WAVES * 64) resample_kernel(long N, int S, 
                     for (int b = 0; b < nf; b += 4) {
                         const f32x4 o = *reinterpret_cast<const f32x4 *>(val + S + b);
                         rank += (o[0] < v) + (o[1] < v) + (o[2] < v) + (o[3] < v);
+                    }
+                } else if (v != v) {                 // a NaN sample: after all S depths and every number among the samples, NaNs in index order
+                    const int j = a - S;
+                    rank = S;
+                    for (int b = 0; b < nf; b += 4) {
+                        const f32x4 o = *reinterpret_cast<const f32x4 *>(val + S + b);
+                        rank += (o[0] == o[0] || b < j) + (o[1] == o[1] || b + 1 < j) + (o[2] == o[2] || b + 2 < j) + (o[3] == o[3] || b + 3 < j);
                     }
                 } else {
                     int lo = 0, hi = S;              // #{z_b <= v}: first index with z > v
@@ -393,9 +404,13 @@ __global__ void __launch_bounds__(RS_WAVES * 64) resample_kernel(long N, int S, 
             for (int a = lane; a < M; a += 64) {
                 const float v = val[a];
                 int rank = 0;
-                for (int b = 0; b < M; ++b) {
-                    const float o = val[b];
-                    rank += (o < v || (o == v && b < a)) ? 1 : 0;
+                if (v != v) {
+                    for (int b = 0; b < M; ++b) rank += (val[b] == val[b] || b < a) ? 1 : 0;
+                } else {
+                    for (int b = 0; b < M; ++b) {
+                        const float o = val[b];
+                        rank += (o < v || (o == v && b < a)) ? 1 : 0;
+                    }
                 }
                 z_out[ray * M + rank] = v;
                 if (src_out != nullptr) src_out[ray * M + rank] = a;
