@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cstdlib>
 #include "sahs_model.hpp"
 
 // Once per (call site, device), safe from several host threads: kernel attributes and device properties belong to a DEVICE,
@@ -23,6 +24,14 @@ inline hipError_t per_device(Flags &flags, F &&action)
     return e;
 }
 }  // namespace sahs_once
+
+// Timing-only switches and tuning aids are read from the environment by SAHS_DIAG builds only (tools/ablate.py); the shipped library,
+// which build.py refuses to build with extra defines, takes the default of each: there this is a constant null.
+#ifdef SAHS_DIAG
+inline const char *sahs_diag_env(const char *name) { return getenv(name); }
+#else
+constexpr const char *sahs_diag_env(const char *) { return nullptr; }
+#endif
 
 namespace SAHS_NS {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
