@@ -314,6 +314,26 @@ int sahs_model_render_rays_rows(int model, const void *packed, const float *fram
                                 const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f, float *raw,
                                 float *weights, float *rows, int row_ld, float *xw, int32_t *src, float *z_new, void *stream);
 
+/* sahs_model_render_rays_rows with SPARSE BRANCHES (fp32; any other precision is handed to sahs_model_render_rays_rows unchanged).  The
+ * composite gives a sample whose sigma + noise is <= 0 the weight exactly 0, and with a background prior it replaces the last sample's
+ * channels, so the colour and seg branches of such samples are never used.  Every radiance evaluation of the chain (both the plain chain and,
+ * with xw / src / z_new, the shared-deformation one) runs as a trunk launch up to fc_alpha, which appends feat, x' and the index of every LIVE
+ * sample to the record workspace, and a branch launch over those records only; rows, z_c, z_f and weights are bit-identical to
+ * sahs_model_render_rays_rows.
+ * raw: the row of a live sample is bit-identical too; of a zero-weight sample only column 15 (sigma) is a network output -- columns 0..14
+ * hold the fc_rgb / fc_seg biases (the FINAL tile as fc_alpha leaves it), finite and the same in both chains, NOT the sample's logits.
+ * ws, ws_bytes: the record workspace, 16-byte aligned; sahs_model_render_sparse_workspace_bytes(model, samples) is the size that takes
+ * `samples` sample evaluations in one slab.  A pass of N * S samples is cut into equal ray slabs whose samples all fit (every sample may
+ * be live), so any size of at least one 128-record tile and one ray's samples works; smaller ones are refused (code 5).  No host
+ * synchronisation: the branch launch reads the record count from device memory.  The launch probe sees ONE record per pass, of the dense
+ * launch's kind and sample count. */
+size_t sahs_model_render_sparse_workspace_bytes(int model, long samples);
+int sahs_model_render_rays_rows_sparse(int model, const void *packed, const float *frame, int precision, long N, const float *rays,
+                                       int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand,
+                                       const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f, float *raw,
+                                       float *weights, float *rows, int row_ld, float *xw, int32_t *src, float *z_new, void *ws, size_t ws_bytes,
+                                       void *stream);
+
 /* ---- optimiser step (the training step's "Adam/LR schedule") ----
  * torch.optim.Adam with weight_decay = 0, amsgrad = False, maximize = False -- what the reference builds
  * (train_stage_rays_auto.py:201-209: getattr(torch.optim, "Adam")(params, lr=cfg.optimizer.lr)) -- as ONE launch over the n contiguous

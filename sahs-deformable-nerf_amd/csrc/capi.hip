@@ -306,6 +306,9 @@ struct ModelFns {
     decltype(&sahs_field_forward_f32_launch) f32;
     decltype(&sahs_field_forward_f32_split_launch) f32_split;
     decltype(&sahs_field_forward_f32_split_bits_launch) f32_split_bits;
+    // ... and the inference render's sparse branches: trunk launch + compacted branch launch, and the bytes of their record workspace
+    decltype(&sahs_field_forward_f32_sparse_launch) f32_sparse;
+    decltype(&sahs_field_f32_sparse_ws_bytes) f32_sparse_ws_bytes;
     // backward (field_bwd.hip): per-layer walk, cut at the (x', w) seam, fused walk
     long (*bwd_ws_words)(long);
     decltype(&sahs_field_backward_launch) bwd;
@@ -330,6 +333,7 @@ struct ModelFns {
         sahs_layout_executed_macs##sfx, sahs_layout_act_part_words##sfx, sahs_layout_act_part_col0##sfx, sahs_layout_bits_part_words##sfx, \
         sahs_fold_conditioning_launch##sfx, sahs_bwd_gemm_precision_state##sfx, sahs_bf16w_exact_leaky_state##sfx,                  \
         sahs_field_forward_f32_launch##sfx, sahs_field_forward_f32_split_launch##sfx, sahs_field_forward_f32_split_bits_launch##sfx, \
+        sahs_field_forward_f32_sparse_launch##sfx, sahs_field_f32_sparse_ws_bytes##sfx,                                              \
         sahs_field_backward_ws_words##sfx, sahs_field_backward_launch##sfx, sahs_field_backward_split_launch##sfx,                  \
         sahs_field_backward_fused_ws_words##sfx, sahs_field_backward_fused_launch##sfx
 static const ModelFns kModels[3] = {
@@ -828,6 +832,101 @@ int sahs_model_render_rays_rows(int model, const void *packed, const float *fram
                              u, noise_f, z_c, z_f, raw, weights, rows + SAHS_ROW_RGB_C, rows + SAHS_ROW_DISP_C, rows + SAHS_ROW_ACC_C,
                              rows + SAHS_ROW_RGB_F, rows + SAHS_ROW_DISP_F, rows + SAHS_ROW_ACC_F, rows + SAHS_ROW_W_BG, rows + SAHS_ROW_DEPTH_F,
                              stream, row_ld, row_ld);
+}
+
+// ---- sparse branches (fp32 inference render): see csrc/field_f32.hip, FIELD_*_TRUNK / FIELD_BRANCH ----
+// One radiance evaluation of the render chain as trunk + branch launches over ray slabs sized to the record workspace; all slabs of the
+// pass under ONE probe record of the kind and sample count the dense launch has.  stage: 0 whole network up to fc_alpha (coarse pass, plain
+// chain's fine pass), 1 radiance trunk on x', w from xw through src.
+static long sparse_capacity(int model, size_t ws_bytes)      // record slots (a multiple of 128) a workspace of ws_bytes holds
+{
+    const ModelFns &m = kModels[model];
+    const long head = m.f32_sparse_ws_bytes(0), rec = m.f32_sparse_ws_bytes(1) - head;
+    if ((long)ws_bytes < head) return 0;
+    long cap = ((long)ws_bytes - head) / rec / 128 * 128;
+    return cap > (1L << 30) ? (1L << 30) : cap;
+}
+static int field_forward_sparse(const char *who, int model, const float *pk, const float *frame, int level, int stage, int part, long N, int S,
+                                const float *rays, int ray_stride, const float *z, float *raw, float *xw, int xw_row, const int32_t *src,
+                                const float *noise, int has_bg, void *ws, long cap, hipStream_t st)
+{
+    const ModelFns &m = kModels[model];
+    const long per = cap / S;      // rays per slab in the worst case: every sample live
+    if (per < 1) return fail(5, "%s: the sparse-branch workspace holds %ld records, one ray has %d samples", who, cap, S);
+    const long nslab = (N + per - 1) / per, step = (N + nslab - 1) / nslab;      // equal slabs
+    int e = probed(probe_kind(model, SAHS_F32, level, part), N * S, st, [&] {
+        for (long r0 = 0; r0 < N; r0 += step) {
+            const long n = N - r0 < step ? N - r0 : step, s0 = r0 * S;
+            hipError_t he = hipMemsetAsync(ws, 0, 8, st);
+            if (he != hipSuccess) return (int)he;
+            int le = m.f32_sparse(pk, frame, level, stage, n * S, S, rays + r0 * ray_stride, ray_stride, z ? z + s0 : nullptr, raw + s0 * 16,
+                                  xw ? xw + r0 * xw_row * 8 : nullptr, xw_row, 0, src ? src + s0 : nullptr, noise ? noise + s0 : nullptr, has_bg, ws,
+                                  cap, num_cus(), st);
+            if (le) return le;
+            le = m.f32_sparse(pk, frame, level, 2, n * S, S, rays + r0 * ray_stride, ray_stride, nullptr, raw + s0 * 16, nullptr, 0, 0, nullptr, nullptr,
+                              has_bg, ws, cap, num_cus(), st);
+            if (le) return le;
+        }
+        return 0;
+    });
+    // (negative: the launcher's own refusals, not HIP errors -- unreachable through the checks above, named in case a caller's change breaks them)
+    if (e == -4) return fail(5, "%s: the sparse-branch launcher refused its record workspace (%ld slots for slabs of %ld samples)", who, cap, step * S);
+    if (e < 0) return fail(4, "%s: the sparse-branch launcher has no stage %d for this model", who, stage);
+    return e ? hip_fail(who, e) : 0;
+}
+
+size_t sahs_model_render_sparse_workspace_bytes(int model, long samples)
+{
+    if (model < 0 || model > 2 || samples < 0 || samples > (1L << 30)) return 0;
+    return (size_t)kModels[model].f32_sparse_ws_bytes((samples + 127) / 128 * 128);
+}
+
+int sahs_model_render_rays_rows_sparse(int model, const void *packed, const float *frame, int precision, long N, const float *rays,
+                                       int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand,
+                                       const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f, float *raw,
+                                       float *weights, float *rows, int row_ld, float *xw, int32_t *src, float *z_new, void *ws, size_t ws_bytes,
+                                       void *stream)
+{
+    const char *who = "sahs_model_render_rays_rows_sparse";
+    REQUIRE_MODEL(model, who);
+    if (precision != SAHS_F32)      // the other precisions have no sparse branches: the dense chain
+        return sahs_model_render_rays_rows(model, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp, white_background, bg, t_rand, noise_c,
+                                           u, noise_f, z_c, z_f, raw, weights, rows, row_ld, xw, src, z_new, stream);
+    if (N == 0) return 0;
+    REQUIRE(rows && row_ld >= SAHS_ROW_COLUMNS, who);
+    REQUIRE(packed && frame && rays && z_c && raw && weights && N >= 0 && Sc >= 1 && nf >= 0 && Sc + nf <= 256 && ray_stride >= 8, who);
+    REQUIRE(nf == 0 || z_f, who);
+    REQUIRE(ws && ALIGNED16(ws) && ALIGNED16(packed) && ALIGNED16(frame) && ALIGNED16(raw) && (!xw || ALIGNED16(xw)), who);
+    const long cap = sparse_capacity(model, ws_bytes);
+    if (cap < 128)
+        return fail(5, "%s: a sparse-branch workspace of %zu bytes holds less than one tile of 128 records (sahs_model_render_sparse_workspace_bytes)",
+                    who, ws_bytes);
+    const bool shared = xw && src && z_new && nf > 0 && kModels[model].deformation_nets;
+    const float *pk = (const float *)packed;
+    const int Sf = Sc + nf, has_bg = bg != nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    int e;
+    if ((e = sahs_stratified_depths(N, Sc, rays, ray_stride, lindisp, t_rand, z_c, stream))) return e;
+    if ((e = field_forward_sparse(who, model, pk, frame, 0, 0, 0, N, Sc, rays, ray_stride, z_c, raw, shared ? xw : nullptr, Sf, nullptr, noise_c, has_bg, ws,
+                                  cap, st)))
+        return e;
+    // (as in the dense chains: the coarse depth and last weight are written only when there is no fine pass)
+    e = sahs_composite_forward_launch(N, Sc, raw, z_c, rays, ray_stride, noise_c, bg, white_background, rows + SAHS_ROW_RGB_C, rows + SAHS_ROW_DISP_C,
+                                      rows + SAHS_ROW_ACC_C, weights, nf == 0 ? rows + SAHS_ROW_DEPTH_F : nullptr, nf == 0 ? rows + SAHS_ROW_W_BG : nullptr,
+                                      row_ld, row_ld, st);
+    if (e) return hip_fail(who, e);
+    if (nf == 0) return 0;
+    if (shared) {      // the deformation nets once per depth (sahs_model_render_rays_rows), the fine pass's radiance nets as trunk + branch
+        if ((e = sahs_resample_merge(N, Sc, nf, z_c, weights, u, z_new, z_f, src, stream))) return e;
+        if ((e = sahs_model_field_forward_split(model, packed, frame, precision, 1, 1, N, nf, rays, ray_stride, z_new, nullptr, xw, Sf, Sc, nullptr, stream))) return e;
+        if ((e = field_forward_sparse(who, model, pk, frame, 1, 1, 2, N, Sf, rays, ray_stride, nullptr, raw, xw, Sf, src, noise_f, has_bg, ws, cap, st))) return e;
+    } else {
+        if ((e = sahs_resample(N, Sc, nf, z_c, weights, u, nullptr, z_f, nullptr, stream))) return e;
+        if ((e = field_forward_sparse(who, model, pk, frame, 1, 0, 0, N, Sf, rays, ray_stride, z_f, raw, nullptr, 0, nullptr, noise_f, has_bg, ws, cap, st))) return e;
+    }
+    e = sahs_composite_forward_launch(N, Sf, raw, z_f, rays, ray_stride, noise_f, bg, white_background, rows + SAHS_ROW_RGB_F, rows + SAHS_ROW_DISP_F,
+                                      rows + SAHS_ROW_ACC_F, weights, rows + SAHS_ROW_DEPTH_F, rows + SAHS_ROW_W_BG, row_ld, row_ld, st);
+    return e ? hip_fail(who, e) : 0;
 }
 
 }  // extern "C"

@@ -133,17 +133,40 @@ __device__ __forceinline__ void grid_blocks(const float *__restrict__ grid, floa
 // the same operands, hence bit-identical results, for 6 % fewer matrix instructions per frame.
 //   xw: (rays, xw_row, 8) floats [x'0 x'1 x'2 w0 w1 . . .]; a launch over (N, S) depths owns columns xw_col0 .. xw_col0 + S - 1
 //   src: (N, S) int32, FIELD_RADIANCE only: column of xw holding sample s of the ray
-enum { FIELD_ALL = 0, FIELD_DEFORM = 1, FIELD_RADIANCE = 2 };
+//
+// The inference render also splits the radiance evaluation at fc_alpha (sparse branches).  The composite gives a sample whose sigma + noise
+// is <= 0 the weight exactly 0 (and replaces the last sample's channels by the background prior), so its colour and seg logits are never
+// used: a TRUNK launch runs the network up to L_ALPHA, stores the FINAL tile as it stands there (rows 0..14 the fc_rgb / fc_seg biases,
+// row 15 sigma) as the sample's raw row, and appends feat, x' and the sample index of every LIVE sample to a compact record buffer; a
+// FIELD_BRANCH launch then runs L_D0B..L_SEG over the records only and overwrites those samples' raw rows.  Columns of an MFMA tile are
+// independent, so a live sample's row has the bits of the one-launch evaluation whatever slot it lands in.
+//   FIELD_ALL_TRUNK = FIELD_ALL up to L_ALPHA, FIELD_RADIANCE_TRUNK = FIELD_RADIANCE up to L_ALPHA, FIELD_BRANCH = the two branches
+enum { FIELD_ALL = 0, FIELD_DEFORM = 1, FIELD_RADIANCE = 2, FIELD_ALL_TRUNK = 3, FIELD_RADIANCE_TRUNK = 4, FIELD_BRANCH = 5 };
+// Record buffer of the sparse branches.  Records are taken in groups of 16 slots (one wave of the branch launch); a group's feat is laid
+// out [k-block 16][lane 64][4] like a weight fragment, so the branch launch loads it with whole 1-KB wave transactions.
+struct SparseArgs {
+    const float *noise;      // trunk: the composite's noise of these samples (N, S), or null
+    unsigned int *count;     // trunk: records appended so far (zeroed by the caller); branch: records to process
+    f32x4 *hdr;              // [cap] {x'0, x'1, x'2, sample index (int bits)}
+    f32x4 *feat;             // [cap / 16][16][64]
+    unsigned int cap;        // slots (a multiple of 128, at least the samples of the trunk launch)
+    int has_bg;              // a background prior replaces the last sample's channels
+};
+constexpr long SPARSE_HEAD_BYTES = 256, SPARSE_RECORD_BYTES = 16 + 16 * 16 * 4;
 template <bool SAVE, int MODE>
 __global__ void __launch_bounds__(F32_THREADS, 2)
 field_forward_f32_kernel(const float *__restrict__ packed, const float *__restrict__ frame, int level, long P, int S,
                          const float *__restrict__ rays, int ray_stride, const float *__restrict__ zvals,
                          float *__restrict__ raw, float *__restrict__ dbg, float *__restrict__ actbuf,
-                         float *__restrict__ xw, int xw_row, int xw_col0, const int *__restrict__ src, uint32_t *__restrict__ bits)
+                         float *__restrict__ xw, int xw_row, int xw_col0, const int *__restrict__ src, uint32_t *__restrict__ bits, SparseArgs sp)
 {
 #if SAHS_MODEL == 2
-    static_assert(MODE == FIELD_ALL, "this model has no deformation nets to split off");
+    static_assert(MODE == FIELD_ALL || MODE == FIELD_ALL_TRUNK || MODE == FIELD_BRANCH, "this model has no deformation nets to split off");
 #endif
+    constexpr bool TRUNK = MODE == FIELD_ALL_TRUNK || MODE == FIELD_RADIANCE_TRUNK;      // stops behind L_ALPHA and appends the live samples' records
+    constexpr bool BRANCH = MODE == FIELD_BRANCH;                                        // walks the records instead of the samples
+    constexpr bool XW_IN = MODE == FIELD_RADIANCE || MODE == FIELD_RADIANCE_TRUNK;       // x', w come from xw through src
+    static_assert(!(SAVE && (TRUNK || BRANCH)), "the sparse branches are an inference path");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Ctx cx;
     cx.stream = packed + PACK_STREAM_OFF + (long)level * STREAM_FLOATS;
@@ -153,12 +176,11 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
     cx.q = cx.lane >> 4;
     cx.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr const Layer *Ly = kProg.layer;
-    constexpr int L_START = (MODE == FIELD_RADIANCE) ? L_T0 : L_FIRST;      // first layer of this launch's walk through the stream
-    cx.wrap_to = (MODE == FIELD_RADIANCE) ? (uint32_t)Ly[L_T0].stream_off : 0u;
-    cx.wrap_at = (MODE == FIELD_DEFORM) ? (uint32_t)Ly[L_T0].stream_off : (uint32_t)STREAM_FLOATS;
+    constexpr int L_START = BRANCH ? L_D0B : (XW_IN ? L_T0 : L_FIRST);      // first layer of this launch's walk through the stream
+    cx.wrap_to = (uint32_t)Ly[L_START].stream_off;
+    cx.wrap_at = (MODE == FIELD_DEFORM) ? (uint32_t)Ly[L_T0].stream_off : (TRUNK ? (uint32_t)Ly[L_D0B].stream_off : (uint32_t)STREAM_FLOATS);
     cx.off = cx.wrap_to;
     const float *grid = packed + PACK_GRID_OFF;
-    const int q = cx.q;
 
     {   // per-level biases (static + folded conditioning) -> LDS, first weight chunk -> buffer 0
         const float *bsrc = frame + FRAME_BIAS_OFF + level * BIAS_FLOATS;
@@ -169,9 +191,19 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         cx.end_chunk();
     }
 
+    if constexpr (BRANCH) {      // the points of this launch are the records the trunk launch left (no host synchronisation in between)
+        const unsigned int n = *sp.count;
+        P = n < sp.cap ? n : sp.cap;
+    }
     const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG;
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         cx.refresh();
+        // (a trunk launch of the 4-layer-trunk models has no rolled layer loop, so the stream offset of every chunk is the same constant
+        // in every tile and LICM precomputes all ~100 LDS-DMA source addresses outside the persistent loop -- a kilobyte of scratch per
+        // lane -- unless the offset is opaque per tile; likewise the encodings' per-lane octave selectors and the lane quarter)
+        int q_tile = cx.q;
+        if constexpr (TRUNK) { asm volatile("" : "+s"(cx.off)); asm volatile("" : "+v"(q_tile)); }
+        const int q = q_tile;
         const long p_raw = tile * F32_PTS_PER_WG + cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15);
         const long p = p_raw < P ? p_raw : P - 1;
         // x' (3) and w (2) are parked in LDS between their uses; the ray direction is re-read where needed: values that stay
@@ -195,18 +227,23 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
 #define SBD(b, w) (sb_on ? bits + (long)(b) * Psv + sb_lane * (uint32_t)((w) >= 128 ? (w) / 128 : 1) : nullptr)
 #define SBR(b, w) (sb_on ? bits_r + (long)(b) * Psv + sb_lane * (uint32_t)((w) >= 128 ? (w) / 128 : 1) : nullptr)
         float x[3] = {0.0f, 0.0f, 0.0f};
-        if constexpr (MODE != FIELD_RADIANCE) {
+        long smp = p;            // the sample of this lane's point: its ray is smp / S, its raw row smp
+        if constexpr (BRANCH) {  // a record: x' -> stash (w is not needed behind the trunk)
+            const f32x4 a = sp.hdr[p];
+            smp = __float_as_int(a[3]);
+            if (q == 0) { stash[0] = a[0]; stash[1] = a[1]; stash[2] = a[2]; }
+        } else if constexpr (!XW_IN) {
             const float *rp = rays + (p / S) * ray_stride;
             const float z = zvals[p];
 #pragma unroll
             for (int i = 0; i < 3; ++i) x[i] = rp[i] + rp[3 + i] * z;          // train_utils.py:115
-        } else if (q == 0) {     // x', w of this sample were computed by the coarse or the deformation launch: fetch through the merge permutation
+        } else if (q == 0) {     // (XW_IN) x', w of this sample were computed by the coarse or the deformation launch: fetch through the merge permutation
             const float *row = xw + ((p / S) * (long)xw_row + src[p]) * 8;
             const f32x4 a = *reinterpret_cast<const f32x4 *>(row);
             stash[0] = a[0]; stash[1] = a[1]; stash[2] = a[2]; stash[3] = a[3]; stash[4] = row[4];
             if (sv_on) { float *d = SVP(act::XW, 16); d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; }   // the grid backward reads x'
         }
-        if constexpr (MODE != FIELD_RADIANCE) {
+        if constexpr (!XW_IN && !BRANCH) {
 #if SAHS_MODEL == 2
         // no deformation nets (use_warp False, use_ambient False): the template is queried at the raw point (models.py:316-327)
         if (q == 0) {
@@ -285,7 +322,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             *reinterpret_cast<f32x4 *>(row) = f32x4{stash[0], stash[1], stash[2], stash[3]};
             row[4] = stash[4];
         }
-        }   // MODE != FIELD_RADIANCE
+        }   // !XW_IN && !BRANCH
         if constexpr (MODE == FIELD_DEFORM) continue;      // the stream has wrapped to the warp field's first layer
         __builtin_amdgcn_wave_barrier();
         if (dump) { dsl[0] = stash[0] - x[0]; dsl[1] = stash[1] - x[1]; dsl[2] = stash[2] - x[2]; dsl[3] = stash[3]; dsl[4] = stash[4]; }
@@ -293,7 +330,12 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         // ---- radiance trunk (modules.py:254-275) ----
         f32x4 fin[1];      // FINAL tile: raw[4q..4q+3] of this lane's point
         f32x4 feat[16];
-        {
+        if constexpr (BRANCH) {      // what the trunk launch left: the FINAL tile behind fc_alpha in the raw row, feat in the record
+            fin[0] = *reinterpret_cast<const f32x4 *>(raw + smp * D_RAW + 4 * q);
+            const f32x4 *rec = sp.feat + (p >> 4) * (16 * 64) + q * 16 + (p & 15);
+#pragma unroll
+            for (int b = 0; b < 16; ++b) feat[b] = rec[b * 64];
+        } else {
             f32x4 h[16];
             {
                 f32x4 in_tr[KB_XYZ + KB_AMB];
@@ -351,13 +393,37 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             dense_sv<SAVE, 16, 0, 16, CHF(L_ALPHA)>(cx, h, nullptr, feat, Ly[L_FEAT].bias_off, false, 1.0f, SV(act::FEAT, 256));
             if (dump) dsl[13] = feat[0][0];
         }
-        dense<16, 0, 1, CHF(L_D0B)>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+        if constexpr (!BRANCH) dense<16, 0, 1, (TRUNK ? CHF(L_START) : CHF(L_D0B))>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+        if constexpr (TRUNK) {
+            if (p_raw < P) *reinterpret_cast<f32x4 *>(raw + p * D_RAW + 4 * q) = fin[0];
+            // live: the composite will give the sample a weight that can be non-zero (render_ops.hip: sg = max(sigma + noise, 0), the same
+            // float expression; the last sample of a ray always has a weight, but with a background prior its channels are replaced)
+            const long ray = p / S;
+            const bool last = (p - ray * S) == S - 1;
+            const float sg = fin[0][3] + (sp.noise != nullptr ? sp.noise[p] : 0.0f);      // sigma: row 15 = value 3 of the q == 3 lanes
+            const bool live = q == 3 && p_raw < P && (last ? sp.has_bg == 0 : sg > 0.0f);
+            const uint32_t mask = (uint32_t)(__ballot(live) >> 48);      // bit j: column j of this wave's 16 samples
+            if (mask != 0u) {
+                uint32_t base = 0u;
+                if (cx.lane == 0) base = atomicAdd(sp.count, (unsigned int)__popc(mask));
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                const int j = cx.lane & 15;
+                const uint32_t slot = base + (uint32_t)__popc(mask & ((1u << j) - 1u));
+                if (((mask >> j) & 1u) && slot < sp.cap) {
+                    f32x4 *rec = sp.feat + (long)(slot >> 4) * (16 * 64) + q * 16 + (slot & 15u);
+#pragma unroll
+                    for (int b = 0; b < 16; ++b) rec[b * 64] = feat[b];
+                    if (q == 0) sp.hdr[slot] = f32x4{stash[0], stash[1], stash[2], __int_as_float((int)p)};
+                }
+            }
+            continue;      // the stream has wrapped to this launch's first layer
+        }
         if (dbg != nullptr && p_raw < P) *reinterpret_cast<f32x4 *>(dsl + 24 + 4 * q) = fin[0];
         // ---- colour branch (modules.py:276-287) ----
         {
             f32x4 in_d[4];
             {
-                const float *rp = rays + (p / S) * ray_stride;
+                const float *rp = rays + (smp / S) * ray_stride;
                 const float rd[3] = {rp[3], rp[4], rp[5]};
                 pe_blocks<3, 4, 2>(rd, q, in_d);                                  // models.py:340 (raw, un-normalised direction)
                 grid_blocks(grid, stash[0], stash[1], stash[2], q, in_d + 2);     // models.py:525
@@ -401,7 +467,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             if (dump) dsl[17] = sn[0][0];
             dense<8, 0, 1, CHF(L_START)>(cx, sn, nullptr, fin, 0, true, 1.0f);
         }
-        if (p_raw < P) *reinterpret_cast<f32x4 *>(raw + p * D_RAW + 4 * q) = fin[0];   // cat((rgb, seg, alpha)) modules.py:295
+        if (p_raw < P) *reinterpret_cast<f32x4 *>(raw + smp * D_RAW + 4 * q) = fin[0];   // cat((rgb, seg, alpha)) modules.py:295
     }
 }
 
@@ -413,7 +479,7 @@ using namespace SAHS_NS;
 template <bool SAVE, int MODE>
 static int launch_field(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, const float *zvals,
                         float *raw, float *dbg, float *actbuf, float *xw, int xw_row, int xw_col0, const int *src, int num_cu, hipStream_t stream,
-                        uint32_t *bits = nullptr)
+                        uint32_t *bits = nullptr, SparseArgs sp = SparseArgs{})
 {
     const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG;
     const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
@@ -425,7 +491,7 @@ static int launch_field(const float *packed, const float *frame, int level, long
     });
     if (ae != hipSuccess) return (int)ae;
     field_forward_f32_kernel<SAVE, MODE><<<grid, F32_THREADS, lds_bytes, stream>>>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, dbg, actbuf,
-                                                                                   xw, xw_row, xw_col0, src, bits);
+                                                                                   xw, xw_row, xw_col0, src, bits, sp);
     return (int)hipGetLastError();
 }
 
@@ -481,6 +547,33 @@ extern "C" int SAHS_SYM(sahs_field_forward_f32_split_bits_launch)(const float *p
         return launch_field<false, FIELD_RADIANCE>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, xw, xw_row, 0, src, num_cu, stream);
     return -2;
 #endif
+}
+
+// The sparse branches (see the kernel's MODE).  stage 0: FIELD_ALL_TRUNK over (rays, zvals), x', w also written to xw when given; stage 1:
+// FIELD_RADIANCE_TRUNK on x', w fetched from xw through src; stage 2: FIELD_BRANCH over the records the trunk launch appended.
+// ws: sahs_field_f32_sparse_ws_bytes(cap) bytes, 16-byte aligned: [record count, zeroed by the caller before the trunk launch | headers |
+// feat groups]; cap: record slots, a multiple of 128 and at least P (every sample may be live).  noise / has_bg: the composite's noise of
+// these samples (or null) and whether it is given a background prior -- what decides which samples are live.
+extern "C" long SAHS_SYM(sahs_field_f32_sparse_ws_bytes)(long cap) { return SPARSE_HEAD_BYTES + cap * SPARSE_RECORD_BYTES; }
+extern "C" int SAHS_SYM(sahs_field_forward_f32_sparse_launch)(const float *packed, const float *frame, int level, int stage, long P, int S,
+                                                    const float *rays, int ray_stride, const float *zvals, float *raw, float *xw, int xw_row,
+                                                    int xw_col0, const int *src, const float *noise, int has_bg, void *ws, long cap, int num_cu,
+                                                    hipStream_t stream)
+{
+    if (P <= 0) return 0;
+    if (ws == nullptr || cap < P || cap % F32_PTS_PER_WG != 0 || cap > (1L << 30)) return -4;
+    char *base = static_cast<char *>(ws);
+    SparseArgs sp{noise, reinterpret_cast<unsigned int *>(base), reinterpret_cast<f32x4 *>(base + SPARSE_HEAD_BYTES),
+                  reinterpret_cast<f32x4 *>(base + SPARSE_HEAD_BYTES + cap * 16), (unsigned int)cap, has_bg};
+    if (stage == 0)
+        return launch_field<false, FIELD_ALL_TRUNK>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream, nullptr, sp);
+    if (stage == 2)      // (P: an upper bound of the record count, for the grid)
+        return launch_field<false, FIELD_BRANCH>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, nullptr, 0, 0, nullptr, num_cu, stream, nullptr, sp);
+#if SAHS_MODEL != 2
+    if (stage == 1)
+        return launch_field<false, FIELD_RADIANCE_TRUNK>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, xw, xw_row, 0, src, num_cu, stream, nullptr, sp);
+#endif
+    return -2;
 }
 
 // words per sample of the saved activations a launch of `part` writes / a backward of `part` reads, and the first act:: column of that

@@ -67,6 +67,11 @@ int sahs_conditioning_backward_launch(const float *flat, const float *audio, con
                                                       const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,     \
                                                       int xw_row, int xw_col0, const int *src, float *actbuf, uint32_t *bits,           \
                                                       int num_cu, hipStream_t stream);                                                  \
+    long sahs_field_f32_sparse_ws_bytes##sfx(long cap);                                                                                 \
+    int sahs_field_forward_f32_sparse_launch##sfx(const float *packed, const float *frame, int level, int stage, long P, int S,        \
+                                                  const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,         \
+                                                  int xw_row, int xw_col0, const int *src, const float *noise, int has_bg, void *ws,    \
+                                                  long cap, int num_cu, hipStream_t stream);                                            \
     /* field_bf16w.hip */                                                                                                                \
     int sahs_bf16w_exact_leaky_state##sfx(int set);                                                                                     \
     int sahs_field_forward_bf16w_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,     \

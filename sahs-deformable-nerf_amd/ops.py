@@ -258,6 +258,46 @@ def render_rays(packed, frame, rays, num_coarse, num_fine, precision=SAHS_F32, l
     return rgb_c, disp_c, acc_c, None, None, None, w_bg, depth_f
 
 
+# upper bound of the record workspace of the sparse branches: ~4 M sample evaluations per slab (a 131,072-ray chunk of 64 coarse + 128 fine
+# samples: 3 + 5 slabs).  Larger slabs buy little (W512 frame on MI355X: 2 GiB +0.6 %, 8 GiB -0.6 % against 4 GiB; LAB_NOTES.md), and the
+# buffer is HBM every renderer holds
+_SPARSE_WORKSPACE_BYTES = 4 << 30
+_SPARSE_BRANCHES = True
+
+
+def sparse_branches(on=None, workspace_bytes=None):
+    """The fp32 inference render (render_rays_rows) skips the colour and seg branches of samples the composite gives the weight exactly 0
+    (sigma + noise <= 0; with a background prior also the last sample of a ray): include/sahs_nerf.h, sahs_model_render_rays_rows_sparse.
+    The rendered rows are bit-identical either way; in the `raw` workspace columns 0..14 of a zero-weight sample then hold the output
+    biases, not its logits.  sparse_branches(False) keeps the dense launches (the A/B reference).  workspace_bytes: upper bound of the
+    record workspace a render allocates (it never takes more than one slab of the chunk's fine pass needs; sparse_workspace_bytes() queries
+    it).  None queries -> bool."""
+    global _SPARSE_BRANCHES, _SPARSE_WORKSPACE_BYTES
+    if on is not None:
+        if not isinstance(on, (bool, int)) or on not in (0, 1, False, True):
+            raise _lib.SahsError("sparse_branches: True or False, not %r" % (on,))
+        _SPARSE_BRANCHES = bool(on)
+    if workspace_bytes is not None:
+        if not isinstance(workspace_bytes, int) or isinstance(workspace_bytes, bool) or workspace_bytes < 1:
+            raise _lib.SahsError("sparse_branches: workspace_bytes must be a positive int, not %r" % (workspace_bytes,))
+        _SPARSE_WORKSPACE_BYTES = workspace_bytes
+    return _SPARSE_BRANCHES
+
+
+def sparse_workspace_bytes():
+    """The upper bound of the sparse branches' record workspace (sparse_branches(workspace_bytes=...))."""
+    return _SPARSE_WORKSPACE_BYTES
+
+
+def sparse_last_count(workspace):
+    """Live records the last trunk launch of a render_rays_rows call appended (the last slab of its last pass), read back from the record
+    workspace kept in ``workspace``: a measurement aid -- it synchronises."""
+    rec = workspace.get("sparse") if workspace else None
+    if rec is None:
+        raise _lib.SahsError("sparse_last_count: this workspace has not been through a sparse render")
+    return int(rec[:4].view(torch.int32).item())
+
+
 ROW_COLUMNS = 36      # SAHS_ROW_* of include/sahs_nerf.h: rgb_c 0:15, disp_c 15, acc_c 16, rgb_f 17:32, disp_f 32, acc_f 33, w_bg 34, depth_f 35
 
 
@@ -311,10 +351,19 @@ def render_rays_rows(packed, frame, rays, num_coarse, num_fine, rows, precision=
         src = ws.get("src")
         if src is None or tuple(src.shape) != (N, Sf) or src.device != dev:
             src = ws["src"] = torch.empty(N, Sf, dtype=torch.int32, device=dev)
-    f, name = _fn("render_rays_rows", arch)
+    extra = []
+    if _SPARSE_BRANCHES and precision == SAHS_F32 and N > 0:
+        # record workspace of the sparse branches: what the fine pass needs in one slab, capped (a smaller one means more slabs)
+        # (the size query answers up to 2^30 samples; a larger pass is cut into slabs anyway)
+        want = min(int(_fn("render_sparse_workspace_bytes", arch)[0](min(N * Sf, 1 << 30))), _SPARSE_WORKSPACE_BYTES)
+        rec = ws.get("sparse")
+        if rec is None or rec.numel() != want or rec.device != dev:
+            rec = ws["sparse"] = torch.empty(want, dtype=torch.uint8, device=dev)
+        extra = [_p(rec), want]
+    f, name = _fn("render_rays_rows_sparse" if extra else "render_rays_rows", arch)
     check(f(_p(packed), _p(frame), precision, N, _p(rays), int(rays.shape[1]), int(num_coarse), int(num_fine),
             int(bool(lindisp)), int(bool(white_background)), _p(bg), _p(t_rand), _p(noise_c), _p(u), _p(noise_f),
-            _p(z_c), _p(z_f), _p(raw), _p(weights), _p(rows), int(rows.stride(0)), _p(xw), _p(src), _p(z_new), _stream()), name)
+            _p(z_c), _p(z_f), _p(raw), _p(weights), _p(rows), int(rows.stride(0)), _p(xw), _p(src), _p(z_new), *extra, _stream()), name)
     return rows
 
 
