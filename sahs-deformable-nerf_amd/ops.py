@@ -2,15 +2,16 @@
 is the HIP library's.  Every function requires CUDA(HIP) fp32 tensors and raises otherwise --
 there is no eager/CPU path here.
 
-autograd: ``RenderRaysFn`` (one ray chunk of predict_and_render_radiance) is the differentiable op: its
-backward runs the HIP backward kernels (composite_backward, field_backward, conditioning_backward) and
-returns gradients for the flat parameter buffer and the audio window.  Importance resampling is not
-differentiated (the reference detaches it, train_utils.py:164).  The stand-alone seams are differentiable too:
-``FieldFn`` behind model(level, x, driving, pose) (parameters and driving input) and ``CompositeFn`` behind
-volume_render_radiance_field (the radiance field), so the reference's own python driver can be run over them.
+autograd: ``RenderRaysFn`` (one ray chunk of predict_and_render_radiance) is the differentiable op.  Its forward picks one strategy -- "shared"
+(split chain, activations kept), "whole" (whole-network saves kept) or "recompute" (depths only) -- and hands its backward the saved tensors
+BY NAME (_save_named / _load_named; None = absent).  Its backward (_RenderBackward: composite backward, field walks, conditioning backward)
+issues the same steps on one stream or, for the per-layer walks of "shared", pairwise on two, and returns gradients for the flat parameter
+buffer and the driving input.  Importance resampling is not differentiated (the reference detaches it, train_utils.py:164).  The stand-alone
+seams are differentiable too: ``FieldFn`` behind model(level, x, driving, pose), ``CompositeFn`` behind volume_render_radiance_field.
 """
 import ctypes
 import os
+import types
 
 import torch
 
@@ -221,6 +222,20 @@ def sample_pdf(bins, weights, num_samples, u=None, want_inds=False):
     return (out, inds) if want_inds else out
 
 
+def _workspace_buffer(ws, dev, name, shape, dtype=torch.float32):
+    """The buffer ``name`` of a render workspace (a dict the caller keeps between calls), made anew when its shape or the device changed."""
+    t = ws.get(name)
+    if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
+        t = ws[name] = torch.empty(*shape, dtype=dtype, device=dev)
+    return t
+
+
+def _req_rows(rows, N):
+    if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[0] == N
+            and rows.shape[1] >= ROW_COLUMNS and rows.stride(1) == 1):
+        raise _lib.SahsError("rows must be a GPU fp32 (N, >=36) tensor with unit column stride")
+
+
 def render_rays(packed, frame, rays, num_coarse, num_fine, precision=SAHS_F32, lindisp=False, white_background=False, bg=None,
                 t_rand=None, noise_c=None, u=None, noise_f=None, workspace=None, arch="audio"):
     """predict_and_render_radiance for one ray chunk -> the reference's 8-tuple (flat shapes)."""
@@ -236,14 +251,7 @@ def render_rays(packed, frame, rays, num_coarse, num_fine, precision=SAHS_F32, l
     dev = rays.device
     Sf = num_coarse + num_fine
     ws = workspace if workspace is not None else {}
-
-    def buf(name, *shape):
-        t = ws.get(name)
-        if t is None or tuple(t.shape) != shape or t.device != dev:
-            t = torch.empty(*shape, dtype=torch.float32, device=dev)
-            ws[name] = t
-        return t
-
+    buf = lambda name, *shape: _workspace_buffer(ws, dev, name, shape)
     z_c, z_f = buf("z_c", N, num_coarse), buf("z_f", N, Sf)
     raw, weights = buf("raw", N, Sf, 16), buf("weights", N, Sf)
     rgb_c, rgb_f = (torch.empty(N, 15, dtype=torch.float32, device=dev) for _ in range(2))
@@ -306,8 +314,7 @@ def composite_forward_rows(raw, z, rays, rows, fine_pass, noise=None, bg=None, w
     returns the dense (N, S) weights."""
     raw, z, rays, noise, bg = _req(raw, "radiance_field"), _req(z, "depth_values"), _req(rays, "rays"), _req(noise, "noise"), _req(bg, "background_prior")
     N, S = z.shape
-    if not (rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[0] == N and rows.shape[1] >= ROW_COLUMNS and rows.stride(1) == 1):
-        raise _lib.SahsError("rows must be a GPU fp32 (N, >=36) tensor with unit column stride")
+    _req_rows(rows, N)
     if weights is None or tuple(weights.shape) != (N, S):
         weights = torch.empty(N, S, dtype=torch.float32, device=z.device)
     check(_lib.lib().sahs_composite_forward_rows(N, S, _p(raw), _p(z), _p(rays), int(rays.shape[1]), _p(noise), _p(bg), int(bool(white_background)),
@@ -325,20 +332,11 @@ def render_rays_rows(packed, frame, rays, num_coarse, num_fine, rows, precision=
     bg, t_rand, noise_c, u, noise_f = (_req(t, n) for t, n in ((bg, "background_prior"), (t_rand, "t_rand"), (noise_c, "noise_c"),
                                                                (u, "u"), (noise_f, "noise_f")))
     N = rays.shape[0]
-    if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[0] == N
-            and rows.shape[1] >= ROW_COLUMNS and rows.stride(1) == 1):
-        raise _lib.SahsError("rows must be a GPU fp32 (N, >=36) tensor with unit column stride")
+    _req_rows(rows, N)
     dev = rays.device
     Sf = num_coarse + num_fine
     ws = workspace if workspace is not None else {}
-
-    def buf(name, *shape):
-        t = ws.get(name)
-        if t is None or tuple(t.shape) != shape or t.device != dev:
-            t = torch.empty(*shape, dtype=torch.float32, device=dev)
-            ws[name] = t
-        return t
-
+    buf = lambda name, *shape: _workspace_buffer(ws, dev, name, shape)
     z_c, z_f = buf("z_c", N, num_coarse), buf("z_f", N, Sf)
     raw, weights = buf("raw", N, Sf, 16), buf("weights", N, Sf)
     xw = src = z_new = None
@@ -348,18 +346,13 @@ def render_rays_rows(packed, frame, rays, num_coarse, num_fine, rows, precision=
     if share_deformation and num_fine > 0 and arch != "nerface_static" and precision in (SAHS_F32, SAHS_BF16, SAHS_BF16X3):
         # extra workspace of the split evaluation: deformed points of every depth, the merge permutation, the new depths
         xw, z_new = buf("xw", N, Sf, 8), buf("z_new", N, num_fine)
-        src = ws.get("src")
-        if src is None or tuple(src.shape) != (N, Sf) or src.device != dev:
-            src = ws["src"] = torch.empty(N, Sf, dtype=torch.int32, device=dev)
+        src = _workspace_buffer(ws, dev, "src", (N, Sf), torch.int32)
     extra = []
     if _SPARSE_BRANCHES and precision == SAHS_F32 and N > 0:
         # record workspace of the sparse branches: what the fine pass needs in one slab, capped (a smaller one means more slabs)
         # (the size query answers up to 2^30 samples; a larger pass is cut into slabs anyway)
         want = min(int(_fn("render_sparse_workspace_bytes", arch)[0](min(N * Sf, 1 << 30))), _SPARSE_WORKSPACE_BYTES)
-        rec = ws.get("sparse")
-        if rec is None or rec.numel() != want or rec.device != dev:
-            rec = ws["sparse"] = torch.empty(want, dtype=torch.uint8, device=dev)
-        extra = [_p(rec), want]
+        extra = [_p(_workspace_buffer(ws, dev, "sparse", (want,), torch.uint8)), want]
     f, name = _fn("render_rays_rows_sparse" if extra else "render_rays_rows", arch)
     check(f(_p(packed), _p(frame), precision, N, _p(rays), int(rays.shape[1]), int(num_coarse), int(num_fine),
             int(bool(lindisp)), int(bool(white_background)), _p(bg), _p(t_rand), _p(noise_c), _p(u), _p(noise_f),
@@ -466,6 +459,21 @@ def alloc_sign_bits(num_samples, mode, arch, device):
     return torch.empty(int(num_samples), words, dtype=torch.int32, device=device) if words > 0 else None
 
 
+def _whole_save_part(act, bits, part, arch, P):
+    """Base pointers (act, bits) of `part` (FIELD_DEFORM | FIELD_RADIANCE) inside a WHOLE-network save of P samples (bits may be None): a saved
+    array of column c starts at float c * P in every save, so the deformation part starts where the save does and the radiance part behind the
+    act columns in front of act::XW / behind sbits::BD_WORDS words per sample.  The kernels move 16 bytes per lane, so both byte offsets must be
+    multiples of 16: in sahs_layout.hpp every act column is a multiple of 16 floats, sbits::words() of 4 words, so the guard never fires today."""
+    if int(part) != FIELD_RADIANCE:
+        return _p(act), _p(bits)
+    words, bwords = _fn("act_words_part", arch)[0], _fn("bits_words_part", arch)[0]
+    offs = 4 * (int(words(FIELD_ALL)) - int(words(FIELD_RADIANCE))) * P, 4 * int(bwords(FIELD_DEFORM)) * P
+    if offs[0] % 16 or offs[1] % 16:
+        raise _lib.SahsError("the radiance part of a whole-network save of N*S = %d samples starts at byte %d (activations) / %d (sign bits): "
+                             "not multiples of 16" % (P, offs[0], offs[1]))
+    return ctypes.c_void_p(act.data_ptr() + offs[0]), None if bits is None else ctypes.c_void_p(bits.data_ptr() + offs[1])
+
+
 def field_forward_split_save(packed, frame, level, mode, rays, xw, z=None, src=None, xw_col0=0, arch="audio", bits=None, precision=SAHS_F32, whole=None):
     """field_forward_split (fp32) that also keeps the activations of the layers it runs -> (raw or None, act).  act is the part's
     own buffer, (P, act_words_part(mode)) floats as dense per-layer planes; only field_backward_split of the same part reads it.
@@ -487,9 +495,7 @@ def field_forward_split_save(packed, frame, level, mode, rays, xw, z=None, src=N
         act, bits = _req(whole[0], "whole act"), _req(whole[1], "whole bits", torch.int32)
         if int(mode) not in (FIELD_DEFORM, FIELD_RADIANCE) or tuple(act.shape) != (N * S, int(words(FIELD_ALL))) or tuple(bits.shape) != (N * S, int(bwords(FIELD_ALL))):
             raise _lib.SahsError("field_forward_split_save(whole): buffers of a FIELD_ALL save of the same samples, filled by a FIELD_DEFORM or FIELD_RADIANCE launch")
-        radiance = int(mode) == FIELD_RADIANCE      # the radiance arrays / planes are the tail of the whole-network tables
-        act_ptr = ctypes.c_void_p(act.data_ptr() + (4 * (int(words(FIELD_ALL)) - int(words(FIELD_RADIANCE))) * N * S if radiance else 0))
-        bits_ptr = ctypes.c_void_p(bits.data_ptr() + (4 * int(bwords(FIELD_DEFORM)) * N * S if radiance else 0))
+        act_ptr, bits_ptr = _whole_save_part(act, bits, mode, arch, N * S)
     else:
         act = torch.empty(N * S, words(int(mode)), dtype=torch.float32, device=rays.device)
         if bits is not None:
@@ -538,16 +544,6 @@ def training_forward_precision(precision=None):
 _TRAIN_FORWARD = os.environ.get("SAHS_TRAIN_FORWARD", "fp32")
 if _TRAIN_FORWARD not in ("fp32", "bf16x3"):
     raise _lib.SahsError("SAHS_TRAIN_FORWARD must be 'fp32' or 'bf16x3', not %r" % (_TRAIN_FORWARD,))
-_IDENTITY_SRC = {}
-
-
-def _identity_src(N, S, device):
-    """src of a radiance launch on the samples of its own pass in order (the coarse pass through the split kernels)"""
-    key = (int(N), int(S), str(device))
-    if key not in _IDENTITY_SRC:
-        _IDENTITY_SRC.clear()
-        _IDENTITY_SRC[key] = torch.arange(S, dtype=torch.int32, device=device).repeat(N, 1).contiguous()
-    return _IDENTITY_SRC[key]
 
 
 def field_backward_split(flat, frame, level, part, act, grad_flat, grad_cond, d_raw=None, xw_grad_in=None, arch="audio", full_act=False, bits=None):
@@ -558,28 +554,22 @@ def field_backward_split(flat, frame, level, part, act, grad_flat, grad_cond, d_
     flat, frame, act = _req(flat, "flat_params"), _req(frame, "frame"), _req(act, "act")
     d_raw, xw_grad_in = _req(d_raw, "d_raw"), _req(xw_grad_in, "xw_grad_in")
     P = act.shape[0]
-    words = _fn("act_words_part", arch)[0]
-    act_ptr = _p(act)
-    if full_act and int(part) in (FIELD_DEFORM, FIELD_RADIANCE):
-        if act.shape[1] != words(3):
-            raise _lib.SahsError("field_backward_split(full_act): the activations were not saved by a whole-network forward")
-        col0 = 0 if int(part) == FIELD_DEFORM else words(3) - words(FIELD_RADIANCE)      # the radiance arrays are the table's tail
-        act_ptr = ctypes.c_void_p(act.data_ptr() + 4 * col0 * P)
-    elif act.shape[1] != words(int(part)):
-        raise _lib.SahsError("field_backward_split: the activations were not saved by a forward of part %d" % part)
+    in_whole = bool(full_act) and int(part) in (FIELD_DEFORM, FIELD_RADIANCE)
+    if act.shape[1] != _fn("act_words_part", arch)[0](3 if in_whole else int(part)):
+        raise _lib.SahsError("field_backward_split(full_act): the activations were not saved by a whole-network forward" if in_whole else
+                             "field_backward_split: the activations were not saved by a forward of part %d" % part)
     if xw_grad_in is not None and xw_grad_in.numel() != P * 8:
         raise _lib.SahsError("field_backward_split: xw_grad_in must hold (P,8)")
     out = torch.empty(P, 8, dtype=torch.float32, device=act.device) if part == FIELD_RADIANCE else None
-    if bits is not None and _FUSED_BACKWARD:
-        bits = _req(bits, "bits", torch.int32)
-        bw = lambda m: int(_fn("bits_words_part", arch)[0](int(m)))
-        saved_mode = 0 if (full_act or int(part) == 3) else int(part)
-        if tuple(bits.shape) != (P, bw(saved_mode)):
+    fused = bits is not None and _FUSED_BACKWARD
+    bits = _req(bits, "bits", torch.int32) if fused else None      # (the per-layer walk reads none)
+    if fused:
+        saved_mode = 0 if (full_act or int(part) == 3) else int(part)      # part 3 takes both halves of a whole-network save, a part of it its own
+        if tuple(bits.shape) != (P, int(_fn("bits_words_part", arch)[0](saved_mode))):
             raise _lib.SahsError("field_backward_split: bits were not written by the forward that saved these activations")
-        # a whole-network save holds [deformation planes | radiance planes]; part 3 takes both, a part of it its own
-        bits_ptr = ctypes.c_void_p(bits.data_ptr() + (4 * bw(FIELD_DEFORM) * P if (full_act and int(part) == FIELD_RADIANCE) else 0))
-        words = int(_fn("field_backward_fused_workspace_words", arch)[0](int(part), P))
-        ws = torch.empty(words, dtype=torch.float32, device=act.device)
+    act_ptr, bits_ptr = _whole_save_part(act, bits, part, arch, P) if in_whole else (_p(act), _p(bits))
+    if fused:
+        ws = torch.empty(int(_fn("field_backward_fused_workspace_words", arch)[0](int(part), P)), dtype=torch.float32, device=act.device)
         f, name = _fn("field_backward_fused", arch)
         check(f(_p(flat), _p(frame), int(level), int(part), P, act_ptr, bits_ptr, _p(d_raw), _p(xw_grad_in), _p(out), _p(grad_flat), _p(grad_cond), _p(ws),
                 _stream()), name)
@@ -654,22 +644,41 @@ def composite_backward(raw, z, rays, noise, bg, white_background, d_rgb, d_disp,
     raw, z, rays = _req(raw, "raw"), _req(z, "z"), _req(rays, "rays")
     N, S = z.shape
     d_raw = torch.empty(N, S, 16, dtype=torch.float32, device=z.device)
-    if loss is not None:
-        if d_weights is not None:
-            raise _lib.SahsError("composite_backward: d_weights and loss together are not supported")
-        lm, lt, lk, st, gsc = (_req(t, n) for t, n in zip(loss, ("loss_map", "loss_target", "loss_mask", "loss_stats", "loss_gscale")))
-        if tuple(lm.shape) != (N, 15) or tuple(lk.shape) != (N, 12) or lt.shape[0] != N or st.numel() < LOSS_STATS_WORDS:
-            raise _lib.SahsError("composite_backward: loss operands (N,15), (N,>=3), (N,12), stats (64,)")
-        gs = [_req(g, n) for g, n in ((d_rgb, "d_rgb"), (d_disp, "d_disp"), (d_acc, "d_acc"), (d_depth, "d_depth"), (d_wlast, "d_wlast"))]
-        check(_lib.lib().sahs_composite_backward_loss(N, S, _p(raw), _p(z), _p(rays), int(rays.shape[1]), _p(_req(noise, "noise")), _p(_req(bg, "bg")),
-                                                       int(bool(white_background)), *[_p(g) for g in gs], _p(lm), _p(lt), int(lt.shape[1]), _p(lk),
-                                                       _p(st), _p(gsc), _p(d_raw), _stream()), "sahs_composite_backward_loss")
+    gs = [_req(g, n) for g, n in ((d_rgb, "d_rgb"), (d_disp, "d_disp"), (d_acc, "d_acc"), (d_depth, "d_depth"), (d_wlast, "d_wlast"))]
+    head = (N, S, _p(raw), _p(z), _p(rays), int(rays.shape[1]), _p(_req(noise, "noise")), _p(_req(bg, "bg")), int(bool(white_background)),
+            *[_p(g) for g in gs])
+    if loss is None:
+        check(_lib.lib().sahs_composite_backward(*head, _p(_req(d_weights, "d_weights")), _p(d_raw), _stream()), "sahs_composite_backward")
         return d_raw
-    gs = [_req(g, n) for g, n in ((d_rgb, "d_rgb"), (d_disp, "d_disp"), (d_acc, "d_acc"), (d_depth, "d_depth"), (d_wlast, "d_wlast"),
-                                  (d_weights, "d_weights"))]
-    check(_lib.lib().sahs_composite_backward(N, S, _p(raw), _p(z), _p(rays), int(rays.shape[1]), _p(_req(noise, "noise")), _p(_req(bg, "bg")),
-                                              int(bool(white_background)), *[_p(g) for g in gs], _p(d_raw), _stream()), "sahs_composite_backward")
+    if d_weights is not None:
+        raise _lib.SahsError("composite_backward: d_weights and loss together are not supported")
+    lm, lt, lk, st, gsc = (_req(t, n) for t, n in zip(loss, ("loss_map", "loss_target", "loss_mask", "loss_stats", "loss_gscale")))
+    if tuple(lm.shape) != (N, 15) or tuple(lk.shape) != (N, 12) or lt.shape[0] != N or st.numel() < LOSS_STATS_WORDS:
+        raise _lib.SahsError("composite_backward: loss operands (N,15), (N,>=3), (N,12), stats (64,)")
+    check(_lib.lib().sahs_composite_backward_loss(*head, _p(lm), _p(lt), int(lt.shape[1]), _p(lk), _p(st), _p(gsc), _p(d_raw), _stream()),
+          "sahs_composite_backward_loss")
     return d_raw
+
+
+def _save_named(ctx, **tensors):
+    """ctx.save_for_backward under names: what a forward hands its backward is asked for by name, never by position.  None = absent."""
+    ctx.saved_names = tuple(tensors)
+    ctx.save_for_backward(*tensors.values())
+
+
+def _load_named(ctx):
+    """The tensors of _save_named as attributes (None where absent); a name that was not saved is an AttributeError."""
+    return types.SimpleNamespace(**dict(zip(ctx.saved_names, ctx.saved_tensors)))
+
+
+def _driving_grad(arch, flat, driving, grad_flat, grad_cond):
+    """grad_cond (what the field walks left for the folded conditioning) -> the driving input's gradient; the audio net's parameters' into grad_flat."""
+    if arch != "audio":      # NeRFaceModel: the driving vector is the expression itself
+        return grad_cond[:76].clone()
+    grad_drv = torch.zeros_like(driving)
+    check(_lib.lib().sahs_conditioning_backward(_p(flat), _p(driving), _p(grad_cond), _p(grad_flat), _p(grad_drv), _stream()),
+          "sahs_conditioning_backward")
+    return grad_drv
 
 
 class CompositeFn(torch.autograd.Function):
@@ -679,20 +688,17 @@ class CompositeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, z, rays, noise, bg, white_background):
         outs = composite_forward(raw, z, rays, noise=noise, bg=bg, white_background=white_background)
-        none = torch.empty(0, device=raw.device)
-        ctx.save_for_backward(raw.detach(), z, rays, noise if noise is not None else none, bg if bg is not None else none, outs[3][:, -1])
-        ctx.cfg = (bool(white_background), noise is not None, bg is not None)
+        _save_named(ctx, raw=raw.detach(), z=z, rays=rays, noise=noise, bg=bg, w_last=outs[3][:, -1])
+        ctx.white_background = bool(white_background)
         return outs
 
     @staticmethod
     def backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth):
-        raw, z, rays, noise, bg, w_last = ctx.saved_tensors
-        white, has_noise, has_bg = ctx.cfg
+        s = _load_named(ctx)
         c = lambda t: None if t is None else t.contiguous().float()
-        d_raw = composite_backward(raw, z, rays, noise if has_noise else None, bg if has_bg else None, white, c(g_rgb), c(g_disp), c(g_acc),
-                                   c(g_depth), None, c(g_w))
-        if has_bg and g_rgb is not None:     # the last sample's 15 channels are used verbatim (:28-35): d = w_last * d_rgb
-            d_raw[:, -1, :15] += w_last[:, None] * g_rgb
+        d_raw = composite_backward(s.raw, s.z, s.rays, s.noise, s.bg, ctx.white_background, c(g_rgb), c(g_disp), c(g_acc), c(g_depth), None, c(g_w))
+        if s.bg is not None and g_rgb is not None:     # the last sample's 15 channels are used verbatim (:28-35): d = w_last * d_rgb
+            d_raw[:, -1, :15] += s.w_last[:, None] * g_rgb
         return d_raw, None, None, None, None, None
 
 
@@ -710,227 +716,218 @@ class FieldFn(torch.autograd.Function):
         # each block keeps its own buffer (a row slice of one big buffer would hand the backward the wrong planes)
         N = z.shape[0]
         rows = max(1, FieldFn.BLOCK // max(1, z.shape[1]))
-        raws, acts = [], []
+        raws, acts = [], {}
         for s in range(0, N, rows):
-            r, a = field_forward_save(packed, frame, level, rays[s:s + rows].contiguous(), z[s:s + rows].contiguous(), arch)
+            r, acts["act%d" % len(raws)] = field_forward_save(packed, frame, level, rays[s:s + rows].contiguous(), z[s:s + rows].contiguous(), arch)
             raws.append(r)
-            acts.append(a)
-        ctx.save_for_backward(flat.detach(), driving.detach(), frame, *acts)
-        ctx.cfg = (level, arch, rows * z.shape[1])
+        _save_named(ctx, flat=flat.detach(), driving=driving.detach(), frame=frame, **acts)
+        ctx.level, ctx.arch, ctx.block, ctx.num_blocks = level, arch, rows * z.shape[1], len(raws)
         return raws[0] if len(raws) == 1 else torch.cat(raws, dim=0)
 
     @staticmethod
     def backward(ctx, g_raw):
-        flat, driving, frame = ctx.saved_tensors[:3]
-        acts = ctx.saved_tensors[3:]
-        level, arch, block = ctx.cfg
-        grad_flat = torch.zeros_like(flat)
-        grad_cond = torch.zeros(128, dtype=torch.float32, device=flat.device)
+        s = _load_named(ctx)
+        acts = [getattr(s, "act%d" % i) for i in range(ctx.num_blocks)]
+        grad_flat = torch.zeros_like(s.flat)
+        grad_cond = torch.zeros(128, dtype=torch.float32, device=s.flat.device)
         g = g_raw.contiguous().float().view(-1, 16)
         if sum(a.shape[0] for a in acts) != g.shape[0]:
             raise _lib.SahsError("FieldFn.backward: %d gradient rows for %d saved samples" % (g.shape[0], sum(a.shape[0] for a in acts)))
         for i, act in enumerate(acts):
-            field_backward(flat, frame, level, act, g[i * block: i * block + act.shape[0]], grad_flat, grad_cond, arch)
-        if arch == "audio":
-            grad_drv = torch.zeros_like(driving)
-            check(_lib.lib().sahs_conditioning_backward(_p(flat), _p(driving), _p(grad_cond), _p(grad_flat), _p(grad_drv), _stream()),
-                  "sahs_conditioning_backward")
-        else:
-            grad_drv = grad_cond[:76].clone()
-        return grad_flat, grad_drv, None, None, None, None, None, None
+            field_backward(s.flat, s.frame, ctx.level, act, g[i * ctx.block: i * ctx.block + act.shape[0]], grad_flat, grad_cond, ctx.arch)
+        return grad_flat, _driving_grad(ctx.arch, s.flat, s.driving, grad_flat, grad_cond), None, None, None, None, None, None
 
 
 class RenderRaysFn(torch.autograd.Function):
     """predict_and_render_radiance (train_utils.py:72-206) for one ray chunk, differentiable w.r.t. the model
     parameters (as the canonical flat buffer) and the audio window.
-
-    forward: the six forward launches; chunks of at most BLOCK_RAYS rays (a training batch) keep the field activations of
-    both passes (19 KB per sample, 7.5 GB for 2048 rays x 192 samples), larger chunks only keep the depths and re-run the field
-    block by block in backward.  backward: per level -- composite backward, field backward -- then the conditioning backward."""
+    forward, by ctx.strategy.  A chunk of at most BLOCK_RAYS rays (a training batch) keeps the field activations of both passes (19 KB per
+    sample, 7.5 GB for 2048 rays x 192 samples): "shared" = the split chain, the deformation nets once per depth; "whole" = a
+    whole-network save per level (SHARE_DEFORMATION = False, and the NeRFaceModel without deformation nets).  "recompute" (larger chunks,
+    num_fine = 0) = render_rays: only the depths are kept and the field is run again block by block in backward.
+    backward (_RenderBackward): per level -- composite backward, field walk(s) -- then the conditioning backward."""
 
     BLOCK_RAYS = 4096
-    SHARE_DEFORMATION = True      # kept path: deformation nets once per depth, forward AND backward (the fine pass's gradient w.r.t. the
-                                  # coarse samples' (x', w) is added at the seam of the coarse pass's backward); False = the plain chain
+    SHARE_DEFORMATION = True      # kept activations: deformation nets once per depth, forward AND backward (the fine pass's gradient w.r.t.
+                                  # the coarse samples' (x', w) is added at the seam of the coarse pass's backward); False = the plain chain
 
     @staticmethod
     def forward(ctx, flat, audio, pose, rays, bg, t_rand, noise_c, u, noise_f, packed, num_coarse, num_fine, lindisp, white_background,
                 arch="audio", loss_target=None, loss_mask=None, loss_weights=None, packed_x3=None):
         """With loss_target (N,>=3), loss_mask (N,12), loss_weights (12,) the op also returns (loss, stats) of the Stage-I objective
         (stage1_loss_forward) and its backward forms that loss's gradient inside the composite backward kernels.
-        packed_x3 (pack_weights(flat, SAHS_BF16X3, arch); kept path, every architecture): the saving forward launches run on the split-operand
-        kernels (training_forward_precision "bf16x3") -- with deformation nets the coarse pass as a deformation + a radiance launch into one
-        whole-network save, without them one whole-network launch per level."""
+        packed_x3 (pack_weights(flat, SAHS_BF16X3, arch); kept activations, every architecture): the saving forward launches run on the
+        split-operand kernels (training_forward_precision "bf16x3") -- with deformation nets the coarse pass as a deformation + a radiance
+        launch into one whole-network save, without them one whole-network launch per level."""
         frame = fold_conditioning(flat.detach(), audio.detach(), pose, arch=arch)
-        ctx.arch = arch
-        ctx.has_loss = loss_target is not None
+        N, dev, Sf = rays.shape[0], rays.device, num_coarse + num_fine
+        kept = N <= RenderRaysFn.BLOCK_RAYS and num_fine > 0
+        shared = kept and RenderRaysFn.SHARE_DEFORMATION and arch != "nerface_static"
+        ctx.strategy = "shared" if shared else "whole" if kept else "recompute"
+        ctx.arch, ctx.num_coarse, ctx.num_fine, ctx.white_background = arch, num_coarse, num_fine, bool(white_background)
+        saved = dict(flat=flat.detach(), audio=audio.detach(), rays=rays, frame=frame, packed=packed, bg=bg, noise_c=noise_c, noise_f=noise_f,
+                     map_c=None, map_f=None, loss_target=None, loss_mask=None, loss_stats=None)
+        # sign bits of the fused walk (None: this backward reads none; of whole-network saves only the NeRFaceModel without deformation nets has one)
+        sign_bits = lambda samples, mode: alloc_sign_bits(samples, mode, arch, dev) if (shared or arch == "nerface_static") else None
+        bits0 = sign_bits(N * num_coarse, FIELD_ALL) if kept else None
+        pk, prec = (packed_x3, SAHS_BF16X3) if (packed_x3 is not None and bits0 is not None) else (packed, SAHS_F32)
+        xw = torch.empty(N, Sf, 8, dtype=torch.float32, device=dev) if shared else None      # x', w of every depth: the split chain's seam
 
-        def with_loss(outs, saved):
-            if not ctx.has_loss:
-                ctx.save_for_backward(*saved)
-                return outs
+        def level_pass(level, z, noise, z_new=None, src=None):
+            # one level of a kept strategy: the saving field launch(es) (shared: as sahs_model_render_rays_rows' split evaluation, whole: as
+            # sahs_render_rays), then the composite
+            nonlocal xw
+            if not shared:
+                bits = bits0 if level == 0 else sign_bits(z.numel(), FIELD_ALL)
+                raw, act = field_forward_save(pk, frame, level, rays, z, arch, bits=bits, precision=prec)
+                saved.update({"act%d" % level: act, "bits%d" % level: bits})
+            elif level == 0 and prec == SAHS_F32:
+                raw, act = field_forward_split_save(pk, frame, 0, FIELD_ALL, rays, xw, z=z, arch=arch, bits=bits0)
+                saved.update(act0=act, bits0=bits0)
+            elif level == 0:      # the split-operand kernels exist per part: two launches fill one whole-network save
+                whole = (torch.empty(N * num_coarse, _fn("act_words_part", arch)[0](FIELD_ALL), dtype=torch.float32, device=dev), bits0)
+                field_forward_split_save(pk, frame, 0, FIELD_DEFORM, rays, xw, z=z, arch=arch, precision=prec, whole=whole)
+                raw, _ = field_forward_split_save(pk, frame, 0, FIELD_RADIANCE, rays, xw, arch=arch, precision=prec, whole=whole,
+                                                  src=torch.arange(num_coarse, dtype=torch.int32, device=dev).repeat(N, 1))      # (its own samples in order)
+                saved.update(act0=whole[0], bits0=bits0)
+            else:                 # deformation nets on the new depths only, radiance nets on every depth through the merge permutation
+                bits_d, bits_r = sign_bits(N * num_fine, FIELD_DEFORM), sign_bits(N * Sf, FIELD_RADIANCE)
+                _, act_d = field_forward_split_save(pk, frame, 1, FIELD_DEFORM, rays, xw, z=z_new, xw_col0=num_coarse, arch=arch, bits=bits_d, precision=prec)
+                raw, act_r = field_forward_split_save(pk, frame, 1, FIELD_RADIANCE, rays, xw, src=src, arch=arch, bits=bits_r, precision=prec)
+                saved.update(act_d=act_d, bits_d=bits_d, act_r=act_r, bits_r=bits_r, src=src)
+                xw = None         # (freed before the fine composite)
+            saved["raw%d" % level] = raw
+            return composite_forward(raw, z, rays, noise, bg, white_background)
+
+        if kept:
+            z_c = stratified_depths(rays, num_coarse, lindisp, t_rand)
+            rgb_c, disp_c, acc_c, w_c, _ = level_pass(0, z_c, noise_c)
+            z_f, z_new, src = resample_merge(z_c, w_c, num_fine, u=u) if shared else (resample(z_c, w_c, num_fine, u), None, None)
+            rgb_f, disp_f, acc_f, w_f, depth_f = level_pass(1, z_f, noise_f, z_new, src)
+            saved.update(z_c=z_c, z_f=z_f)
+            outs = (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, w_f[:, -1].contiguous(), depth_f)
+        else:
+            ws = {}
+            outs = render_rays(packed, frame, rays, num_coarse, num_fine, precision=SAHS_F32, lindisp=lindisp, white_background=white_background,
+                               bg=bg, t_rand=t_rand, noise_c=noise_c, u=u, noise_f=noise_f, workspace=ws, arch=arch)
+            saved.update(z_c=ws["z_c"].clone(), z_f=ws["z_f"].clone() if num_fine > 0 else None)
+        if loss_target is not None:
             tgt, msk = loss_target.detach().float().contiguous(), loss_mask.detach().float().contiguous()
             rgb_f = outs[3] if num_fine > 0 else None
             stats = stage1_loss_forward(outs[0], rgb_f, tgt, msk, loss_weights.detach().float().contiguous())
-            ctx.n_base = len(saved)
-            ctx.save_for_backward(*saved, outs[0], rgb_f if rgb_f is not None else torch.empty(0, device=rays.device), tgt, msk, stats)
+            saved.update(map_c=outs[0], map_f=rgb_f, loss_target=tgt, loss_mask=msk, loss_stats=stats)
             ctx.mark_non_differentiable(stats)
-            return tuple(outs) + (stats[0].clone(), stats)
-
-        none = torch.empty(0, device=rays.device)
-        ctx.cfg = (num_coarse, num_fine, bool(white_background), bg is not None, noise_c is not None, noise_f is not None)
-        ctx.kept = rays.shape[0] <= RenderRaysFn.BLOCK_RAYS and num_fine > 0
-        ctx.shared = ctx.kept and RenderRaysFn.SHARE_DEFORMATION and arch != "nerface_static"
-        if ctx.shared:   # the launch chain of sahs_model_render_rays_rows' split evaluation, with the activations of every launch kept
-            N = rays.shape[0]
-            z_c = stratified_depths(rays, num_coarse, lindisp, t_rand)
-            xw = torch.empty(N, num_coarse + num_fine, 8, dtype=torch.float32, device=rays.device)
-            sb = lambda samples, mode: alloc_sign_bits(samples, mode, arch, rays.device)      # (None: this architecture's backward reads none)
-            bits_c, bits_d, bits_r = sb(N * num_coarse, FIELD_ALL), sb(N * num_fine, FIELD_DEFORM), sb(N * (num_coarse + num_fine), FIELD_RADIANCE)
-            x3 = packed_x3 is not None and bits_c is not None
-            pk, prec = (packed_x3, SAHS_BF16X3) if x3 else (packed, SAHS_F32)
-            if x3:
-                act_c = torch.empty(N * num_coarse, _fn("act_words_part", arch)[0](FIELD_ALL), dtype=torch.float32, device=rays.device)
-                field_forward_split_save(pk, frame, 0, FIELD_DEFORM, rays, xw, z=z_c, arch=arch, precision=prec, whole=(act_c, bits_c))
-                raw_c, _ = field_forward_split_save(pk, frame, 0, FIELD_RADIANCE, rays, xw, src=_identity_src(N, num_coarse, rays.device), arch=arch,
-                                                    precision=prec, whole=(act_c, bits_c))
-            else:
-                raw_c, act_c = field_forward_split_save(packed, frame, 0, FIELD_ALL, rays, xw, z=z_c, arch=arch, bits=bits_c)
-            rgb_c, disp_c, acc_c, w_c, _ = composite_forward(raw_c, z_c, rays, noise_c, bg, white_background)
-            z_f, z_new, src = resample_merge(z_c, w_c, num_fine, u=u)
-            _, act_d = field_forward_split_save(pk, frame, 1, FIELD_DEFORM, rays, xw, z=z_new, xw_col0=num_coarse, arch=arch, bits=bits_d, precision=prec)
-            raw_f, act_r = field_forward_split_save(pk, frame, 1, FIELD_RADIANCE, rays, xw, src=src, arch=arch, bits=bits_r, precision=prec)
-            del xw
-            rgb_f, disp_f, acc_f, w_f, depth_f = composite_forward(raw_f, z_f, rays, noise_f, bg, white_background)
-            outs = (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, w_f[:, -1].contiguous(), depth_f)
-            ctx.has_bits = bits_c is not None
-            return with_loss(outs, (flat.detach(), audio.detach(), rays, z_c, z_f, frame, packed,
-                                    *[t if t is not None else none for t in (bg, noise_c, noise_f)], raw_c, act_c, raw_f, act_r, act_d, src,
-                                    *((bits_c, bits_r, bits_d) if bits_c is not None else ())))
-        if ctx.kept:     # the same launch chain as sahs_render_rays, with the field activations kept
-            # (the NeRFaceModel without deformation nets trains here: its saves also write the sign bits of its fused walk)
-            N = rays.shape[0]
-            sb = lambda samples: alloc_sign_bits(samples, FIELD_ALL, arch, rays.device) if arch == "nerface_static" else None
-            z_c = stratified_depths(rays, num_coarse, lindisp, t_rand)
-            bits_c = sb(N * num_coarse)
-            x3 = packed_x3 is not None and bits_c is not None
-            pk, prec = (packed_x3, SAHS_BF16X3) if x3 else (packed, SAHS_F32)
-            raw_c, act_c = field_forward_save(pk, frame, 0, rays, z_c, arch, bits=bits_c, precision=prec)
-            rgb_c, disp_c, acc_c, w_c, _ = composite_forward(raw_c, z_c, rays, noise_c, bg, white_background)
-            z_f = resample(z_c, w_c, num_fine, u)
-            bits_f = sb(z_f.numel())
-            raw_f, act_f = field_forward_save(pk, frame, 1, rays, z_f, arch, bits=bits_f, precision=prec)
-            rgb_f, disp_f, acc_f, w_f, depth_f = composite_forward(raw_f, z_f, rays, noise_f, bg, white_background)
-            outs = (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, w_f[:, -1].contiguous(), depth_f)
-            ctx.has_bits = bits_c is not None
-            return with_loss(outs, (flat.detach(), audio.detach(), rays, z_c, z_f, frame, packed,
-                                    *[t if t is not None else none for t in (bg, noise_c, noise_f)], raw_c, act_c, raw_f, act_f,
-                                    *((bits_c, bits_f) if bits_c is not None else ())))
-        ws = {}
-        outs = render_rays(packed, frame, rays, num_coarse, num_fine, precision=SAHS_F32, lindisp=lindisp, white_background=white_background,
-                           bg=bg, t_rand=t_rand, noise_c=noise_c, u=u, noise_f=noise_f, workspace=ws, arch=arch)
-        return with_loss(outs, (flat.detach(), audio.detach(), rays, ws["z_c"].clone(), ws["z_f"].clone() if num_fine > 0 else none, frame, packed,
-                                *[t if t is not None else none for t in (bg, noise_c, noise_f)]))
+            outs = tuple(outs) + (stats[0].clone(), stats)
+        _save_named(ctx, **saved)
+        return outs
 
     @staticmethod
     def backward(ctx, g_rgb_c, g_disp_c, g_acc_c, g_rgb_f, g_disp_f, g_acc_f, g_wbg, g_depth_f, g_loss=None, g_stats=None):
-        flat, audio, rays, z_c, z_f, frame, packed, bg, noise_c, noise_f = ctx.saved_tensors[:10]
-        loss_ops = None
-        if ctx.has_loss and g_loss is not None:
-            map_c, map_f, l_tgt, l_msk, l_stats = ctx.saved_tensors[ctx.n_base:ctx.n_base + 5]
-            loss_ops = {0: map_c, 1: map_f}
-            gscale = g_loss.detach().float().reshape(1).contiguous()
-        kept = dict(zip((0, 1), (ctx.saved_tensors[10:12], ctx.saved_tensors[12:14]))) if ctx.kept else None
-        act_d, src = (ctx.saved_tensors[14], ctx.saved_tensors[15]) if ctx.shared else (None, None)
-        bits_c, bits_r, bits_d = ctx.saved_tensors[16:19] if (ctx.shared and getattr(ctx, "has_bits", False)) else (None, None, None)
-        kept_bits = {0: bits_c, 1: bits_r}
-        if ctx.kept and not ctx.shared and getattr(ctx, "has_bits", False):      # the whole-network saves' sign bits, per level
-            kept_bits = {0: ctx.saved_tensors[14], 1: ctx.saved_tensors[15]}
-        xwg_coarse = None      # shared deformation: the fine pass's seam gradient that belongs to the coarse samples
-        nc, nf, white, has_bg, has_nc, has_nf = ctx.cfg
-        bg = bg if has_bg else None
-        noise_c = noise_c if has_nc else None
-        noise_f = noise_f if has_nf else None
-        dev = rays.device
-        grad_flat = torch.zeros_like(flat)
-        grad_cond = torch.zeros(128, dtype=torch.float32, device=dev)
-        grad_audio = torch.zeros_like(audio)
-        c = lambda t: None if t is None else t.contiguous().float()
-        N = rays.shape[0]
-        both_levels = loss_ops is not None or (any(g is not None for g in (g_rgb_f, g_disp_f, g_acc_f, g_depth_f, g_wbg)) and
-                                               any(g is not None for g in (g_rgb_c, g_disp_c, g_acc_c)))
-        # the fused walk is two full-chip persistent launches per part: run side by side they starve each other (measured: 14.0 ms per step on two
-        # streams, 13.3 on one), so the pairwise two-stream issue below is for the per-layer walks only (fused_backward(False))
-        fused_walk = bits_c is not None and _FUSED_BACKWARD
-        if (ctx.shared and nf > 0 and kept is not None and N <= RenderRaysFn.BLOCK_RAYS and both_levels and not fused_walk
+        # level -> (d_rgb, d_disp, d_acc, d_depth, d_wlast); coarse only (train_utils.py:148-149): depth and weights[:, -1] are the COARSE pass's
+        grads = ({1: (g_rgb_f, g_disp_f, g_acc_f, g_depth_f, g_wbg), 0: (g_rgb_c, g_disp_c, g_acc_c, None, None)} if ctx.num_fine > 0 else
+                 {0: (g_rgb_c, g_disp_c, g_acc_c, g_depth_f, g_wbg)})
+        bw = _RenderBackward(ctx, _load_named(ctx), grads, g_loss)
+        # the fused walk is two full-chip persistent launches per part: run side by side they starve each other (measured: 14.0 ms per step on
+        # two streams, 13.3 on one), so the pairwise two-stream issue is for the per-layer walks only (fused_backward(False))
+        if (ctx.strategy == "shared" and not (bw.s.bits0 is not None and _FUSED_BACKWARD) and bw.has_grad[0] and bw.has_grad[1]
                 and not os.environ.get("SAHS_BWD_ONE_STREAM")):
-            # The two levels' radiance walks are independent of each other, and so are the two deformation walks that follow them (coarse
-            # depths / new depths): each pair runs on two streams.  A walk is ~75 dependent GEMM launches whose fixed costs (ring fill, a
-            # K loop with one workgroup per CU, the atomic epilogue, ramp and tail: DESIGN.md section 7) leave most of the chip idle for
-            # part of every launch; the other stream's launches fill it.  Everything the walks add into grad_flat / grad_cond is atomic.
-            main, side = torch.cuda.current_stream(dev), _side_stream(dev)
-            gb = lambda grads: [None if g is None else c(g) for g in grads]
-            lv_loss = lambda level: None if loss_ops is None else (loss_ops[level].contiguous(), l_tgt.contiguous(), l_msk.contiguous(), l_stats, gscale)
-            (raw1, act1), (raw0, act0) = kept[1], kept[0]
-            cc = lambda t: None if t is None else t.contiguous()
-            d_raw1 = composite_backward(raw1, cc(z_f), cc(rays), cc(noise_f), cc(bg), white, *gb((g_rgb_f, g_disp_f, g_acc_f, g_depth_f, g_wbg)), loss=lv_loss(1))
-            d_raw0 = composite_backward(raw0, cc(z_c), cc(rays), cc(noise_c), cc(bg), white, *gb((g_rgb_c, g_disp_c, g_acc_c, None, None)), loss=lv_loss(0))
-            grad_cond_side = torch.zeros_like(grad_cond)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                g_c0 = field_backward_split(flat, frame, 0, FIELD_RADIANCE, act0, grad_flat, grad_cond_side, d_raw=d_raw0.view(-1, 16), arch=ctx.arch, full_act=True,
-                                            bits=bits_c)
-            g_f = field_backward_split(flat, frame, 1, FIELD_RADIANCE, act1, grad_flat, grad_cond, d_raw=d_raw1.view(-1, 16), arch=ctx.arch, bits=bits_r)
-            xwg_coarse, g_new = route_xw_grad(src, g_f, nc)
-            main.wait_stream(side)
-            xwg0 = g_c0 + xwg_coarse          # the seam gradient of the coarse samples: their own radiance walk's + the fine pass's share
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                field_backward_split(flat, frame, 0, FIELD_DEFORM, act0, grad_flat, grad_cond_side, xw_grad_in=xwg0, arch=ctx.arch, full_act=True, bits=bits_c)
-            field_backward_split(flat, frame, 1, FIELD_DEFORM, act_d, grad_flat, grad_cond, xw_grad_in=g_new, arch=ctx.arch, bits=bits_d)
-            main.wait_stream(side)
-            grad_cond += grad_cond_side
-            for t in (d_raw0, xwg0, grad_cond_side, act0, grad_flat, flat, frame) + ((bits_c,) if bits_c is not None else ()):      # made on this stream, used on the side stream: the
-                t.record_stream(side)                                                     # allocator must not hand them out again before it is done
-            g_c0.record_stream(main)                                                      # (and the other way round)
-            N = 0                             # (the block loop below has nothing left to do)
-        for s in range(0, N, RenderRaysFn.BLOCK_RAYS):
-            e = min(N, s + RenderRaysFn.BLOCK_RAYS)
-            sl = slice(s, e)
-            rb = rays[sl].contiguous()
-            bgb = None if bg is None else bg[sl].contiguous()
-            if nf > 0:
-                passes = ((1, z_f, noise_f, (g_rgb_f, g_disp_f, g_acc_f, g_depth_f, g_wbg)),
-                          (0, z_c, noise_c, (g_rgb_c, g_disp_c, g_acc_c, None, None)))
-            else:     # coarse only (train_utils.py:148-149): depth and weights[:, -1] of the 8-tuple are the COARSE pass's
-                passes = ((0, z_c, noise_c, (g_rgb_c, g_disp_c, g_acc_c, g_depth_f, g_wbg)),)
-            for level, z, noise, grads in passes:
-                lvl_loss = None
-                if loss_ops is not None:      # with nf == 0 the only pass is level 0 and its map is the coarse one
-                    lvl_loss = (loss_ops[level][sl].contiguous(), l_tgt[sl].contiguous(), l_msk[sl].contiguous(), l_stats, gscale)
-                if lvl_loss is None and all(g is None for g in grads) and not (level == 0 and xwg_coarse is not None):
+            bw.two_streams()
+        else:
+            bw.one_stream()
+        return (bw.grad_flat, _driving_grad(ctx.arch, bw.s.flat, bw.s.audio, bw.grad_flat, bw.grad_cond)) + (None,) * 17
+
+
+class _RenderBackward:
+    """RenderRaysFn.backward: saved state `s`, upstream gradients per level (fine first), the buffers every walk adds into (atomically), and
+    the steps that its two issue orders, one_stream and two_streams, are made of."""
+
+    def __init__(self, ctx, s, grads, g_loss):
+        self.s, self.grads, self.arch, self.strategy, self.num_coarse, self.white = s, grads, ctx.arch, ctx.strategy, ctx.num_coarse, ctx.white_background
+        self.z, self.noise, self.loss_map = {0: s.z_c, 1: s.z_f}, {0: s.noise_c, 1: s.noise_f}, {0: s.map_c, 1: s.map_f}
+        self.gscale = g_loss.detach().float().reshape(1).contiguous() if (s.loss_stats is not None and g_loss is not None) else None
+        self.has_grad = {level: self.gscale is not None or any(g is not None for g in gs) for level, gs in grads.items()}
+        self.grad_flat = torch.zeros_like(s.flat)
+        self.grad_cond = torch.zeros(128, dtype=torch.float32, device=s.rays.device)
+
+    def composite(self, level, raw, sl=slice(None)):
+        """The composite backward of rays `sl` of a level, with the level's loss operands (level 0: the coarse map) -> d_raw (P,16)."""
+        s = self.s
+        cut = lambda t: None if t is None else t[sl].contiguous()
+        loss = None if self.gscale is None else (cut(self.loss_map[level]), cut(s.loss_target), cut(s.loss_mask), s.loss_stats, self.gscale)
+        return composite_backward(raw, cut(self.z[level]), cut(s.rays), cut(self.noise[level]), cut(s.bg), self.white,
+                                  *[None if g is None else g[sl].contiguous().float() for g in self.grads[level]], loss=loss).view(-1, 16)
+
+    def whole_walk(self, level, act, bits, d_raw, xw_grad_in=None):
+        """A level's whole-network save walked at once: fused when sign bits were kept, else per-layer; shared level 0 adds the fine pass's seam gradient."""
+        s = self.s
+        if self.strategy == "shared" or bits is not None:
+            field_backward_split(s.flat, s.frame, level, 3, act, self.grad_flat, self.grad_cond, d_raw=d_raw, xw_grad_in=xw_grad_in, arch=self.arch, bits=bits)
+        else:
+            field_backward(s.flat, s.frame, level, act, d_raw, self.grad_flat, self.grad_cond, self.arch)
+
+    def part_walk(self, level, part, d_raw=None, xw_grad_in=None, side=None):
+        """shared strategy: the walk of FIELD_RADIANCE (-> its seam gradient) or FIELD_DEFORM of a level (level 1 saved its parts apart,
+        level 0 as one whole-network save); side = (stream, its grad_cond): issued there, behind everything the current stream holds so far."""
+        s = self.s
+        act, bits = (s.act0, s.bits0) if level == 0 else (s.act_r, s.bits_r) if part == FIELD_RADIANCE else (s.act_d, s.bits_d)
+        walk = lambda grad_cond: field_backward_split(s.flat, s.frame, level, part, act, self.grad_flat, grad_cond, d_raw=d_raw, xw_grad_in=xw_grad_in,
+                                                      arch=self.arch, full_act=(level == 0), bits=bits)
+        if side is None:
+            return walk(self.grad_cond)
+        main = torch.cuda.current_stream(s.rays.device)
+        side[0].wait_stream(main)
+        with torch.cuda.stream(side[0]):
+            out = walk(side[1])
+        # (all made on the main stream: the allocator must not hand them out again before the side stream is done; the walk's result the other way round)
+        for t in (s.flat, s.frame, act, bits, self.grad_flat, side[1], d_raw, xw_grad_in):
+            if t is not None:
+                t.record_stream(side[0])
+        if out is not None:
+            out.record_stream(main)
+        return out
+
+    def fine_walks(self, d_raw):
+        """shared, level 1: radiance walk, seam routing through the merge permutation, deformation walk of the new depths -> the coarse samples' seam gradient."""
+        g_f = self.part_walk(1, FIELD_RADIANCE, d_raw=d_raw)
+        xwg_coarse, g_new = route_xw_grad(self.s.src, g_f, self.num_coarse)
+        self.part_walk(1, FIELD_DEFORM, xw_grad_in=g_new)
+        return xwg_coarse
+
+    def one_stream(self):
+        """BLOCK_RAYS rays at a time (a kept chunk is one block; recompute: the whole-network saving forward again per block), level by level.
+        A level without upstream gradient is skipped -- but shared level 0 still runs when the fine pass left a seam gradient for its samples."""
+        s, N = self.s, self.s.rays.shape[0]
+        for start in range(0, N, RenderRaysFn.BLOCK_RAYS):
+            sl = slice(start, min(N, start + RenderRaysFn.BLOCK_RAYS))
+            xwg_coarse = None
+            for level in self.grads:
+                if not self.has_grad[level] and xwg_coarse is None:
                     continue
-                zb = z[sl].contiguous()
-                raw, act = kept[level] if kept is not None else field_forward_save(packed, frame, level, rb, zb, ctx.arch)
-                nb = None if noise is None else noise[sl].contiguous()
-                gb = [None if g is None else c(g[sl]) for g in grads]
-                d_raw = composite_backward(raw, zb, rb, nb, bgb, white, *gb, loss=lvl_loss)
-                if ctx.shared:      # (kept path: one block, sl covers every ray)
-                    if level == 1:
-                        g_f = field_backward_split(flat, frame, 1, FIELD_RADIANCE, act, grad_flat, grad_cond, d_raw=d_raw.view(-1, 16), arch=ctx.arch, bits=kept_bits[1])
-                        xwg_coarse, g_new = route_xw_grad(src, g_f, nc)
-                        field_backward_split(flat, frame, 1, FIELD_DEFORM, act_d, grad_flat, grad_cond, xw_grad_in=g_new, arch=ctx.arch, bits=bits_d)
-                        del g_f, g_new
-                    else:
-                        field_backward_split(flat, frame, 0, 3, act, grad_flat, grad_cond, d_raw=d_raw.view(-1, 16), xw_grad_in=xwg_coarse, arch=ctx.arch,
-                                             bits=kept_bits[0])
-                elif kept is not None and kept_bits[level] is not None:      # whole network, sign bits kept: the fused walk (per-layer: fused_backward(False))
-                    field_backward_split(flat, frame, level, 3, act, grad_flat, grad_cond, d_raw=d_raw.view(-1, 16), arch=ctx.arch, bits=kept_bits[level])
+                if (self.strategy, level) == ("shared", 1):
+                    xwg_coarse = self.fine_walks(self.composite(1, s.raw1, sl))
+                    continue
+                if self.strategy == "recompute":
+                    (raw, act), bits = field_forward_save(s.packed, s.frame, level, s.rays[sl].contiguous(), self.z[level][sl].contiguous(), self.arch), None
                 else:
-                    field_backward(flat, frame, level, act, d_raw.view(-1, 16), grad_flat, grad_cond, ctx.arch)
+                    raw, act, bits = getattr(s, "raw%d" % level), getattr(s, "act%d" % level), getattr(s, "bits%d" % level)
+                d_raw = self.composite(level, raw, sl)
+                self.whole_walk(level, act, bits, d_raw, xwg_coarse)
                 del raw, act, d_raw
-        if ctx.arch == "audio":
-            check(_lib.lib().sahs_conditioning_backward(_p(flat), _p(audio), _p(grad_cond), _p(grad_flat), _p(grad_audio), _stream()),
-                  "sahs_conditioning_backward")
-        else:       # NeRFaceModel: the driving vector is the expression itself
-            grad_audio = grad_cond[:76].clone()
-        return (grad_flat, grad_audio) + (None,) * 17
+
+    def two_streams(self):
+        """shared strategy, per-layer walks, both levels: the two radiance walks are independent of each other, and so are the two deformation
+        walks that follow (coarse / new depths; level 0 as part 2, then part 1 of its whole-network save), so each pair runs on two streams.  A
+        walk is ~75 dependent GEMM launches whose fixed costs leave most of the chip idle; the other stream's fill it."""
+        s = self.s
+        d_raw1, d_raw0 = self.composite(1, s.raw1), self.composite(0, s.raw0)
+        side = (_side_stream(s.rays.device), torch.zeros_like(self.grad_cond))
+        main = torch.cuda.current_stream(s.rays.device)
+        g_c0 = self.part_walk(0, FIELD_RADIANCE, d_raw=d_raw0, side=side)
+        g_f = self.part_walk(1, FIELD_RADIANCE, d_raw=d_raw1)
+        xwg_coarse, g_new = route_xw_grad(s.src, g_f, self.num_coarse)
+        main.wait_stream(side[0])
+        xwg0 = g_c0 + xwg_coarse          # the seam gradient of the coarse samples: their own radiance walk's + the fine pass's share
+        self.part_walk(0, FIELD_DEFORM, xw_grad_in=xwg0, side=side)
+        self.part_walk(1, FIELD_DEFORM, xw_grad_in=g_new)
+        main.wait_stream(side[0])
+        self.grad_cond += side[1]

@@ -222,6 +222,91 @@ def test_shared_deformation_training_matches_plain_chain(arch, weights_mod):
         off += n
 
 
+_ONE_LEVEL_EAGER = {}      # loss pattern -> (per-tensor parameter gradients, driving-input gradient) of the eager restatement
+
+
+def _one_level_loss(outs, pattern, A):
+    if pattern == "fine_only":
+        return (outs[3] * A[1]).sum() + 0.3 * outs[7].sum() + 0.2 * outs[6].sum()
+    return (outs[0] * A[0]).sum() + 0.1 * outs[1].sum()
+
+
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("pattern", ["fine_only", "coarse_only"])
+def test_one_level_losses_through_render_rays_fn(pattern, fused, weights_mod):
+    """A loss that reaches RenderRaysFn through ONE level only: fine_only (the coarse pass gets no upstream gradient, but in the shared
+    strategy its deformation walk still has to run for the seam gradient the fine pass leaves on the coarse samples) and coarse_only
+    (the fine pass is skipped altogether), on the fused and on the per-layer walks.  37 rays x (40 + 37) samples: 1480 and 2849 samples,
+    both off the 128-point tile.  Against plain autograd of the eager restatement on the same draws (every parameter tensor and the
+    driving input within 2e-2 of the tensor's scale: the bound, and therefore the network, of
+    test_train_step_2048_rays_vs_eager_autograd; a tensor the loss does not reach must get exactly zero), and the shared strategy
+    against the plain chain at the bounds of test_shared_deformation_training_matches_plain_chain."""
+    from oracle import torch_eager as TE
+    ops = pkg("ops")
+    dev = torch.device("cuda:0")
+    sd_np = weights_mod.hash_state_dict(0, 8.0, 30.0)
+    fw = weights_mod.flatten_state_dict(sd_np)
+    gen = torch.Generator(device=dev).manual_seed(11)
+    N, nc, nf = 37, 40, 37
+    drv = torch.randn(16, 29, device=dev, generator=gen)
+    pose = torch.from_numpy(np.concatenate([np.eye(3), [[0.0], [0.0], [0.8]]], 1).astype(np.float32)).to(dev)
+    rays = torch.zeros(N, 8, device=dev)
+    rays[:, 2] = 0.8
+    rays[:, 3:6] = torch.randn(N, 3, device=dev, generator=gen) * 0.15 + torch.tensor([0, 0, -1.0], device=dev)
+    rays[:, 6], rays[:, 7] = 0.483771, 1.083771
+    bg = torch.cat([torch.rand(N, 3, device=dev, generator=gen), torch.ones(N, 1, device=dev), torch.zeros(N, 11, device=dev)], 1)
+    t_rand, u = torch.rand(N, nc, device=dev, generator=gen), torch.rand(N, nf, device=dev, generator=gen)
+    noise_c, noise_f = torch.randn(N, nc, device=dev, generator=gen) * 0.1, torch.randn(N, nc + nf, device=dev, generator=gen) * 0.1
+    A = [torch.randn(N, 15, device=dev, generator=gen) for _ in range(2)]
+    if pattern not in _ONE_LEVEL_EAGER:
+        sd_t = {k: torch.from_numpy(v).to(dev).requires_grad_(True) for k, v in sd_np.items()}
+        d = drv.clone().requires_grad_(True)
+        outs = TE.render_rays(TE.EagerField(sd_t, num_coarse=nc, num_fine=nf), rays, d, pose, nc, nf, 131072, bg=bg, t_rand=t_rand,
+                              noise_c=noise_c, u=u, noise_f=noise_f)
+        _one_level_loss(outs, pattern, A).backward()
+        _ONE_LEVEL_EAGER[pattern] = ({k: (torch.zeros_like(v) if v.grad is None else v.grad.clone()) for k, v in sd_t.items()}, d.grad.clone())
+    ref_params, ref_drv = _ONE_LEVEL_EAGER[pattern]
+    res = {}
+    was_fused = ops.fused_backward()
+    try:
+        ops.fused_backward(fused)
+        for share in (False, True):
+            ops.RenderRaysFn.SHARE_DEFORMATION = share
+            flat = torch.from_numpy(fw).to(dev).requires_grad_(True)
+            d = drv.clone().requires_grad_(True)
+            packed = ops.pack_weights(flat.detach(), arch="audio")
+            outs = ops.RenderRaysFn.apply(flat, d, pose, rays, bg, t_rand, noise_c, u, noise_f, packed, nc, nf, False, False, "audio")
+            _one_level_loss(outs, pattern, A).backward()
+            torch.cuda.synchronize()
+            res[share] = (flat.grad.clone(), d.grad.clone())
+    finally:
+        ops.RenderRaysFn.SHARE_DEFORMATION = True
+        ops.fused_backward(was_fused)
+    figures = {}
+    for share in (False, True):      # against the eager autograd, per tensor
+        off = 0
+        for name, shape in weights_mod.canonical_spec("audio"):
+            n = int(np.prod(shape))
+            ref = ref_params[name].reshape(-1)
+            scale = float(ref.abs().max()) + 1e-12
+            figures[(share, name)] = float((res[share][0][off:off + n] - ref).abs().max()) / scale
+            off += n
+        figures[(share, "driving input")] = float((res[share][1] - ref_drv).abs().max()) / (float(ref_drv.abs().max()) + 1e-12)
+    print(json.dumps({"pattern": pattern, "fused": fused, "worst_vs_eager": {str(s): max(v for (sh, _), v in figures.items() if sh == s) for s in (False, True)}}))
+    for (share, name), err in figures.items():
+        assert err <= 2e-2, "%s (shared=%s): %.3e of scale" % (name, share, err)
+    for k, nm in ((0, "parameters"), (1, "driving input")):      # shared strategy against the plain chain
+        a, b = res[False][k], res[True][k]
+        scale = float(a.abs().max())
+        assert scale > 0 and float((a - b).abs().max()) <= 2e-4 * scale, (nm, float((a - b).abs().max()), scale)
+    off = 0
+    for name, shape in weights_mod.canonical_spec("audio"):
+        n = int(np.prod(shape))
+        na, nb = float(res[False][0][off:off + n].norm()), float(res[True][0][off:off + n].norm())
+        assert abs(na - nb) <= 1e-3 * na + 1e-12, (name, na, nb)
+        off += n
+
+
 def test_stage1_loss_kernel_vs_loss_modules():
     """sahs_stage1_loss_forward against the torch statement of the reference's loss modules (pinned to the reference's own classes by
     tests/golden/losses.npz on CPU): ragged ray count, an empty class, a one-ray class, coarse-only; and its gradient, formed inside
