@@ -1,5 +1,5 @@
 // bf16x3_pipe.hpp -- the split-operand dense layer on the bf16 matrix pipe, shared by the forward kernels of field_bf16x3.hip and the
-// backward chain kernels of field_bwd_fused.hip.
+// backward chain kernels of field_bwd_chain.hip.
 //
 // Every operand is split into two bf16 numbers, x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (16-17 significant bits together),
 // and a product is three MFMAs with fp32 accumulation,

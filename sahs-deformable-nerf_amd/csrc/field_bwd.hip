@@ -18,6 +18,7 @@
 #include "field_bwd_gemm.hpp"
 #include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
+#include "bwd_program.hpp"
 
 namespace SAHS_NS {
 
@@ -39,8 +40,7 @@ __device__ __forceinline__ void pe_grad(const float *enc, const float *denc, flo
     }
 }
 
-constexpr int DIN_LD = 16 * (KB_XYZ + KB_AMB);   // row of the gradient wrt [PE(x') blocks | PE(w) blocks]: 96 | 128 | 64
-constexpr int DIN_AMB = 16 * KB_XYZ;             // where the PE(w) part starts
+constexpr int DIN_AMB = 16 * KB_XYZ;             // where the PE(w) part of a DIN_LD-wide row starts
 
 // one coordinate's gradient through its encoding (pe_grad, one axis)
 template <int D, int L, int INC>
@@ -361,6 +361,39 @@ struct Bwd {
         sahs::copy2d(st, 2048, P, N, src, lds_, dst, ldd, mode);
         check();
     }
+    // ---- the fused walk: a part's job table from the backward's layer table (bwd_program.hpp: kFwd) ----
+    const float *flat = nullptr, *frame = nullptr, *actbuf = nullptr;
+    float *grad_flat = nullptr, *grad_cond = nullptr;
+    float *db = nullptr;   // bias-gradient scratch (DB_SCRATCH floats, zeroed)
+    int dbo = 0;           // running offset into it
+    float *scratch_db(int n) { float *p = db + dbo; dbo += (n + 3) / 4 * 4; return p; }
+    void defer_add(const float *src, float *dst, int n)
+    {
+        if (naxpy < MAX_AXPY_JOBS) axpys.j[naxpy++] = AxpyJob{src, dst, n};
+        else if (!err) err = (int)hipErrorOutOfMemory;
+    }
+    void defer_consts(long woff, long ld, int rows, int col0, int cols, const float *dbl, const float *c, float *dc)
+    {
+        if (nconst < MAX_CONST_JOBS) {
+            consts.j[nconst++] = ConstJob{flat + woff, grad_flat + woff, dbl, c, dc, ld, rows, cols, col0};
+            const_maxcols = cols > const_maxcols ? cols : const_maxcols;
+        } else if (!err) err = (int)hipErrorOutOfMemory;
+    }
+    // The jobs of layer E: dW[:, an input segment's columns] += dZ^T X per input segment, X the segment's saved plane, the bias gradient
+    // riding on the first; then per range of per-frame-constant columns their gradients from the bias gradient -- which such a layer
+    // leaves in scratch (this call's db on its own), added to dbias at the end of the walk.
+    void layer_jobs(TnList &L, const bwp::Dense &E, int level, const float *dZ, long ldz, int M, float *dW, float *dbias)
+    {
+        float *dl = E.nfold ? scratch_db(E.rows) : dbias;
+        for (int s = 0; s < E.nin; ++s)
+            L.add(dZ, ldz, M, actbuf + (long)E.in[s].plane * P, E.in[s].width, E.in[s].valid, dW + E.in[s].col0, E.ld, s == 0 ? dl : nullptr);
+        if (E.nfold) defer_add(dl, dbias, E.rows);
+        for (int f = 0; f < E.nfold; ++f) {
+            const bool pose = E.fold[f].which == 1;      // (Fold::which; grad_cond is laid out like the frame's head: [0:76] d_driving, [80:116] d_pose36)
+            defer_consts(E.w_off[level], E.ld, E.rows, E.fold[f].src_col, E.fold[f].count, dl, frame + (pose ? FRAME_POSE_OFF : FRAME_DRV_OFF),
+                         grad_cond + (pose ? FRAME_POSE_OFF : FRAME_DRV_OFF));
+        }
+    }
 };
 
 }  // namespace
@@ -375,6 +408,9 @@ constexpr int HEAD_W_SEG = 0, HEAD_W_RGB = 16 * 128, HEAD_W_ALPHA = 2 * 16 * 128
 constexpr long HEAD_FLOATS = HEAD_DB + 64;
 extern "C" long SAHS_SYM(sahs_field_backward_ws_words)(long P) { return P * (256L * 3 + DIN_LD + 32 + 12) + DB_SCRATCH + 2 * GRID_FLOATS + WAL_FLOATS + P * 8 + HEAD_FLOATS; }
 
+// The per-layer walk.  It states the network by hand -- every tensor, leading dimension, column offset and plane below -- and is NOT moved onto
+// the layer table the fused walk is generated from (bwd_program.hpp): it is the reference the tests compare the fused walk against, and a
+// shared table would turn a mistake in the table into a common-mode error that those tests cannot see.
 // grad_cond: [0:76] d_driving, [80:116] d_pose36 (accumulated).  grad_flat: accumulated.  d_raw: (P,16).
 // part (bit 1: deformation nets, bit 2: radiance nets; 0 = 3 = everything) cuts the walk at its seam, the gradient w.r.t. the deformed
 // point and the ambient coordinate, (P,8) rows [dx'0 dx'1 dx'2 . dw0 dw1 . .]: the radiance part alone leaves it in xwg_out, the
@@ -667,7 +703,6 @@ static int fused_rad(const float *flat, const float *frame, int level, long P, c
 {
     Bwd b{stream, P};
     const FlatOffsets &F = kFlat;
-    const FlatOffsets::Lvl &Lv = F.lvl[level];
     float *dact_mem = ws, *dgridf = dact_mem + P * RAD_PLANES, *din_a = dgridf + P * 32, *din_b = din_a + P * DIN_LD, *dxw = din_b + P * DIN_LD,
           *dw = dxw + P * 4, *db = dw + P * 4, *grid_cl = db + DB_SCRATCH, *dgrid_cl = grid_cl + GRID_FLOATS, *bstream = dgrid_cl + GRID_FLOATS,
           *heads = bstream + FusedWs::stream(2);
@@ -691,60 +726,26 @@ static int fused_rad(const float *flat, const float *frame, int level, long P, c
         grid_transpose_kernel<<<tb, 256, 0, stream>>>(dgrid_cl, grad_flat + F.grid, 1); b.check();
         if (USE_DEFORM) { encode_backward_kernel<<<2048, 256, 0, stream>>>(P, actbuf, din_a, din_b, dxw, dw, xwg_out); b.check(); }
     }
-    // ---- every weight gradient of the part: one job table ----
-    const float *A = actbuf;
-    auto AC = [&](int c) { return A + (long)c * P; };
-    auto DA = [&](int c) { return dact + (long)c * P; };
+    // ---- every weight gradient of the part: one job table, in this order (TnList cuts items by cost in list order, tiles of one job share an XCD) ----
+    b.flat = flat; b.frame = frame; b.actbuf = actbuf; b.grad_flat = grad_flat; b.grad_cond = grad_cond; b.db = db;
     auto G = [&](long off) { return grad_flat + off; };
-    const float *p36 = frame + FRAME_POSE_OFF, *drv = frame + FRAME_DRV_OFF;
-    const float *trc = TRUNK_SEES_POSE ? p36 : drv;
-    float *d_trc = grad_cond + (TRUNK_SEES_POSE ? 80 : 0);
-    int dbo = 0;
-    auto scratch_db = [&](int n) { float *p = db + dbo; dbo += (n + 3) / 4 * 4; return p; };
-    auto defer_add = [&](const float *src, float *dst, int n) { if (b.naxpy < MAX_AXPY_JOBS) b.axpys.j[b.naxpy++] = AxpyJob{src, dst, n}; else if (!b.err) b.err = (int)hipErrorOutOfMemory; };
-    auto defer_consts = [&](long woff, long ld, int rows, int col0, int cols, const float *dbl, const float *c, float *dc) {
-        if (b.nconst < MAX_CONST_JOBS) {
-            b.consts.j[b.nconst++] = ConstJob{flat + woff, G(woff), dbl, c, dc, ld, rows, cols, col0};
-            b.const_maxcols = cols > b.const_maxcols ? cols : b.const_maxcols;
-        } else if (!b.err) b.err = (int)hipErrorOutOfMemory;
-    };
+    int order[hb::NUM_LAYERS_H], n = 0;
+    for (int id : {hb::H_SEG, hb::H_RGB, hb::H_ALPHA, hb::H_S3, hb::H_D3, hb::H_S2, hb::H_D2, hb::H_S1, hb::H_D1, hb::H_S0, hb::H_D0, hb::H_FEAT}) order[n++] = id;
+    for (int i = TR_LAYERS - 1; i >= 0; --i) order[n++] = hb::H_T0 + i;
     TnList L;
-    // the three heads read the whole d_raw row against 16-row scratch gradients (rows 3..14 fc_seg, 0..2 fc_rgb, 15 fc_alpha)
-    L.add(d_raw, 16, 16, AC(act::S + 384), BR_H, BR_H, heads + HEAD_G_SEG, BR_H, heads + HEAD_DB);
-    L.add(d_raw, 16, 16, AC(act::C + 384), BR_H, BR_H, heads + HEAD_G_RGB, BR_H);
-    L.add(d_raw, 16, 16, AC(act::FEAT), TR_H, TR_H, heads + HEAD_G_ALPHA, TR_H);
-    defer_add(heads + HEAD_G_SEG + 3 * BR_H, G(Lv.segout_w), N_SEG * BR_H);
-    defer_add(heads + HEAD_DB + 3, G(Lv.segout_b), N_SEG);
-    defer_add(heads + HEAD_DB, G(Lv.rgb_b), 3);
-    defer_add(heads + HEAD_DB + 15, G(Lv.alpha_b), 1);
-    defer_add(heads + HEAD_G_RGB, G(Lv.rgb_w), 3 * BR_H);
-    defer_add(heads + HEAD_G_ALPHA + 15 * TR_H, G(Lv.alpha_w), TR_H);
-    for (int i = 3; i >= 1; --i) {
-        L.add(DA(act::S + 128 * i), BR_H, BR_H, AC(act::S + 128 * (i - 1)), BR_H, BR_H, G(Lv.seg_w[i]), BR_H, G(Lv.seg_b[i]));
-        L.add(DA(act::C + 128 * i), BR_H, BR_H, AC(act::C + 128 * (i - 1)), BR_H, BR_H, G(Lv.dir_w[i]), BR_H, G(Lv.dir_b[i]));
-    }
-    L.add(DA(act::S), BR_H, BR_H, AC(act::FEAT), TR_H, TR_H, G(Lv.seg_w[0]), TR_H, G(Lv.seg_b[0]));
-    L.add(DA(act::C), BR_H, BR_H, AC(act::FEAT), TR_H, TR_H, G(Lv.dir_w[0]), D_DIR_IN, G(Lv.dir_b[0]));
-    L.add(DA(act::C), BR_H, BR_H, AC(act::DIR), 32, D_DIR, G(Lv.dir_w[0]) + TR_H, D_DIR_IN);
-    L.add(DA(act::C), BR_H, BR_H, AC(act::GRID), 32, D_GRID, G(Lv.dir_w[0]) + TR_H + D_DIR, D_DIR_IN);
-    L.add(DA(act::FEAT), TR_H, TR_H, AC(act::T + (TR_LAYERS - 1) * 256), TR_H, TR_H, G(Lv.feat_w), TR_H, G(Lv.feat_b));
-    for (int i = TR_LAYERS - 1; i >= 1; --i) {
-        const long ldw = (i == 3) ? TR_H + D_TR_IN : TR_H;
-        float *dl = (i == 3) ? scratch_db(TR_H) : G(Lv.xyz_b[i]);
-        L.add(DA(act::T + 256 * i), TR_H, TR_H, AC(act::T + 256 * (i - 1)), TR_H, TR_H, G(Lv.xyz_w[i]), ldw, dl);
-        if (i == 3) {
-            L.add(DA(act::T + 768), TR_H, TR_H, AC(act::PEX), 16 * KB_XYZ, D_XYZ, G(Lv.xyz_w[3]) + TR_H, ldw);
-            if (D_AMB > 0) L.add(DA(act::T + 768), TR_H, TR_H, AC(act::PEW), 16 * KB_AMB, D_AMB, G(Lv.xyz_w[3]) + TR_H + D_XYZ, ldw);
-            defer_add(dl, G(Lv.xyz_b[3]), TR_H);
-            defer_consts(Lv.xyz_w[3], ldw, TR_H, TR_H + D_XYZ + D_AMB, D_TR_CONST, dl, trc, d_trc);
+    float *head_db = heads + HEAD_DB;      // the column sums of d_raw = the three heads' bias gradients: with the first head's job
+    for (int k = 0; k < n; ++k) {
+        const bwp::Dense &E = bwp::kFwd.d[order[k]];
+        if (E.out != bwp::HEAD) {
+            b.layer_jobs(L, E, level, dact + (long)E.out * P, E.rows, E.rows, G(E.w_off[level]), G(E.b_off[level]));
+            continue;
         }
-    }
-    {
-        float *dl = scratch_db(TR_H);
-        L.add(DA(act::T), TR_H, TR_H, AC(act::PEX), 16 * KB_XYZ, D_XYZ, G(Lv.xyz_w[0]), D_TR_IN, dl);
-        if (D_AMB > 0) L.add(DA(act::T), TR_H, TR_H, AC(act::PEW), 16 * KB_AMB, D_AMB, G(Lv.xyz_w[0]) + D_XYZ, D_TR_IN);
-        defer_add(dl, G(Lv.xyz_b[0]), TR_H);
-        defer_consts(Lv.xyz_w[0], D_TR_IN, TR_H, D_XYZ + D_AMB, D_TR_CONST, dl, trc, d_trc);
+        // a head reads the whole d_raw row against a 16-row scratch gradient, of which rows kshift .. are its own (3..14 fc_seg, 0..2 fc_rgb, 15 fc_alpha)
+        float *hg = heads + (order[k] == hb::H_SEG ? HEAD_G_SEG : (order[k] == hb::H_RGB ? HEAD_G_RGB : HEAD_G_ALPHA));
+        b.layer_jobs(L, E, level, d_raw, D_RAW, D_RAW, hg, head_db);
+        head_db = nullptr;
+        b.defer_add(hg + E.kshift * E.ld, G(E.w_off[level]), E.rows * E.ld);
+        b.defer_add(heads + HEAD_DB + E.kshift, G(E.b_off[level]), E.rows);
     }
     if (b.err) return b.err;
     e = L.launch(P, b.zero, num_cu, stream, f32);
@@ -758,7 +759,6 @@ static int fused_def(const float *flat, const float *frame, long P, const float 
                      float *grad_cond, float *ws, int num_cu, hipStream_t stream)
 {
     Bwd b{stream, P};
-    const FlatOffsets &F = kFlat;
     float *dact = ws, *g3 = dact + P * DEF_PLANES, *dw4 = g3 + P * 4, *db = dw4 + P * 4, *bstream = db + DB_SCRATCH;
     b.zero = db + DB_SCRATCH - 64;
     if (hipMemsetAsync(db, 0, sizeof(float) * DB_SCRATCH, stream) != hipSuccess) return (int)hipGetLastError();
@@ -768,42 +768,14 @@ static int fused_def(const float *flat, const float *frame, long P, const float 
     e = f32 ? SAHS_SYM(sahs_bwd_chain_f32_def_launch)(bstream, P, xwg, actbuf, bits, dact, g3, dw4, num_cu, stream)
             : SAHS_SYM(sahs_bwd_chain_def_launch)(bstream, P, xwg, actbuf, bits, dact, g3, dw4, num_cu, stream);
     if (e) return e;
-    auto AC = [&](int c) { return actbuf + (long)c * P; };
-    auto DA = [&](int c) { return dact + (long)c * P; };
-    auto G = [&](long off) { return grad_flat + off; };
-    const float *p36 = frame + FRAME_POSE_OFF, *drv = frame + FRAME_DRV_OFF;
-    float *d_drv = grad_cond + 0, *d_p36 = grad_cond + 80;
-    int dbo = 0;
-    auto scratch_db = [&](int n) { float *p = db + dbo; dbo += (n + 3) / 4 * 4; return p; };
-    auto defer_add = [&](const float *src, float *dst, int n) { if (b.naxpy < MAX_AXPY_JOBS) b.axpys.j[b.naxpy++] = AxpyJob{src, dst, n}; else if (!b.err) b.err = (int)hipErrorOutOfMemory; };
-    auto defer_consts = [&](long woff, long ld, int rows, int col0, int cols, const float *dbl, const float *c, float *dc) {
-        if (b.nconst < MAX_CONST_JOBS) {
-            b.consts.j[b.nconst++] = ConstJob{flat + woff, G(woff), dbl, c, dc, ld, rows, cols, col0};
-            b.const_maxcols = cols > b.const_maxcols ? cols : b.const_maxcols;
-        } else if (!b.err) b.err = (int)hipErrorOutOfMemory;
-    };
+    b.flat = flat; b.frame = frame; b.actbuf = actbuf; b.grad_flat = grad_flat; b.grad_cond = grad_cond; b.db = db;
     TnList L;
-    auto net = [&](const float *head_dy, int head_rows, long fw, long fb, const long *w, const long *bs, int Hn, int col) {
-        L.add(head_dy, 4, head_rows, AC(col + 5 * Hn), Hn, Hn, G(fw), Hn, G(fb));
-        for (int i = 5; i >= 1; --i) {
-            const long ldw = (i == 4) ? Hn + D_DEF_IN : Hn;
-            float *dl = (i == 4) ? scratch_db(Hn) : G(bs[i]);
-            L.add(DA(col + i * Hn), Hn, Hn, AC(col + (i - 1) * Hn), Hn, Hn, G(w[i]), ldw, dl);
-            if (i == 4) {
-                L.add(DA(col + 4 * Hn), Hn, Hn, AC(act::E), 16 * KB_XYZ, D_XYZ, G(w[4]) + Hn, ldw);
-                defer_add(dl, G(bs[4]), Hn);
-                defer_consts(w[4], ldw, Hn, Hn + D_XYZ, D_DRV, dl, drv, d_drv);
-                defer_consts(w[4], ldw, Hn, Hn + D_XYZ + D_DRV, D_POSE, dl, p36, d_p36);
-            }
-        }
-        float *dl = scratch_db(Hn);
-        L.add(DA(col), Hn, Hn, AC(act::E), 16 * KB_XYZ, D_XYZ, G(w[0]), D_DEF_IN, dl);
-        defer_add(dl, G(bs[0]), Hn);
-        defer_consts(w[0], D_DEF_IN, Hn, D_XYZ, D_DRV, dl, drv, d_drv);
-        defer_consts(w[0], D_DEF_IN, Hn, D_XYZ + D_DRV, D_POSE, dl, p36, d_p36);
-    };
-    net(dw4, AMB_DIM, F.hyp_fw, F.hyp_fb, F.hyp_w, F.hyp_b, HYP_H, act::HH);
-    net(g3, 3, F.warp_fw, F.warp_fb, F.warp_w, F.warp_b, WARP_H, act::WH);
+    for (int id : {hb::H_HF, hb::H_H5, hb::H_H4, hb::H_H3, hb::H_H2, hb::H_H1, hb::H_H0, hb::H_WF, hb::H_W5, hb::H_W4, hb::H_W3, hb::H_W2, hb::H_W1, hb::H_W0}) {
+        const bwp::Dense &E = bwp::kFwd.d[id];
+        // (a head's dZ: the (P,4) rows of pre-activation gradients the chain kernel left)
+        const float *dZ = E.out != bwp::HEAD ? dact + (long)E.out * P : (id == hb::H_HF ? dw4 : g3);
+        b.layer_jobs(L, E, 0, dZ, E.out != bwp::HEAD ? E.rows : 4, E.rows, grad_flat + E.w_off[0], grad_flat + E.b_off[0]);
+    }
     if (b.err) return b.err;
     e = L.launch(P, b.zero, num_cu, stream, f32);
     if (e) return e;

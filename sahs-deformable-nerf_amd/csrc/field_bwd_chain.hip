@@ -9,7 +9,7 @@
 //   * the (leaky-)ReLU derivative taken from the sign bits the saving forward wrote (sahs_layout.hpp: sbits; 1 bit per value instead of the
 //     saved fp32 activation), applied as v_bfe_i32 + v_bfi_b32 on the value's way into the conversion,
 //   * every dZ tile stored once, fp32, into the plane of its layer (the act:: layout: dZ of a layer sits where its activation sits in
-//     the saved-activation buffer) -- the operands of the weight-gradient launch that follows (field_bwd.hip: gemm_tn_jobs_kernel).
+//     the saved-activation buffer) -- the operands of the weight-gradient launch that follows (field_bwd_gemm.hip: gemm_tn_jobs_kernel).
 // Same arithmetic as the per-layer split-operand GEMMs it replaces (hi*hi + hi*lo + lo*hi, fp32 accumulation), a different summation
 // order.  Built once per model (sahs_model.hpp): the layer programs below follow each model's trunk (8 layers for the AudioFaceModel, 4 for
 // the NeRFaceModels, skip layer 3 in all) and the NeRFaceModel without deformation nets (SAHS_MODEL 2) has no deformation chain and no
@@ -19,6 +19,7 @@
 #include "sahs_common.hpp"
 #include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
+#include "bwd_program.hpp"
 #include "bf16_pipe.hpp"
 #include "bf16x3_pipe.hpp"
 
@@ -26,21 +27,10 @@ namespace SAHS_NS {
 namespace bwc {
 using namespace hx3;
 
-// ---- the backward layer program ----------------------------------------------------------------------------------------------------
-// A backward layer multiplies A = (part of) W^T: its output rows are INPUT features of the forward layer (W's columns col0 ..), its K
-// index runs over the forward layer's OUTPUT features (W's rows).  Up to three K segments (dfeat sums three branches), up to two row
-// ranges (the encodings' gradient: PE(x') columns, then PE(w) columns).  The heads read the 16-float d_raw row [drgb3 | dseg12 | dsigma]
-// as a 32-feature block whose k = d_raw column: kshift places the head's weight rows (fc_seg: rows 0..11 at k = 3..14).  A head layer on its
-// own runs over TWO blocks, the second all zeros: dense_x's counted LDS waits assume at least AP = 4 k-steps per tile.
-struct SegB { long w_off[2]; int ld, kshift, krows, blocks; };
-struct RowB { int rows, col0, valid; };
-struct LayerB {
-    int NT32, KB32, nseg; SegB seg[3];
-    int nrow; RowB row[2];
-    long stream_off;      // halfwords, in this part's stream
-    int chunk_hw;
-};
-// (the trunk from fc_feat back: T<i>IN = the encodings' rows of a layer that reads [PE(x') | PE(w)], T<i> = its hidden rows)
+// ---- the backward layer program: bwd_program.hpp's, in 32-row tiles and 32-gradient k-blocks (halfwords of hi + lo), chunked as dense_x
+// streams it.  The enums name its layers in the order of bwp::make_rad / make_def = the order of the stream = the order in which the
+// kernels below walk it (the trunk from fc_feat back: T<i>IN = the encodings' rows of a layer that reads [PE(x') | PE(w)], T<i> = its
+// hidden rows) ------------------------------------------------------------------------------------------------------------------------
 #if SAHS_MODEL == 0
 enum RadLayer { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATIN, R_FEAT, R_T7, R_T6, R_T5, R_T4, R_T3IN, R_T3, R_T2, R_T1, R_T0IN, R_COUNT };
 #elif SAHS_MODEL == 1
@@ -49,140 +39,40 @@ enum RadLayer { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_F
 enum RadLayer { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATIN, R_FEAT, R_T3, R_T2, R_T1, R_COUNT };
 #endif
 enum DefLayer { D_HF, D_H5, D_H4, D_H3, D_H2, D_H1, D_WF, D_W5, D_W4, D_W3, D_W2, D_W1, D_COUNT };
-constexpr int DIN_W = 16 * (KB_XYZ + KB_AMB);      // a row of the encodings' gradient (din_a, din_b): 96 | 128 floats (SAHS_MODEL 0 | 1)
-static_assert(!USE_DEFORM || DIN_W == 96 || DIN_W == 128, "the encodings' rows are one 32-row tile short of or exactly the layer's 4 tiles");
-template <int N> struct ProgB { LayerB layer[N]; long stream_hw; };
-
-constexpr LayerB mkb(int NT32, SegB s0, RowB r0, SegB s1 = {{0, 0}, 0, 0, 0, 0}, SegB s2 = {{0, 0}, 0, 0, 0, 0}, RowB r1 = {0, 0, 0})
-{
-    LayerB L{};
-    L.NT32 = NT32;
-    L.seg[0] = s0; L.seg[1] = s1; L.seg[2] = s2;
-    L.nseg = 1 + (s1.blocks > 0) + (s2.blocks > 0);
-    L.KB32 = s0.blocks + s1.blocks + s2.blocks;
-    L.row[0] = r0; L.row[1] = r1;
-    L.nrow = 1 + (r1.rows > 0);
-    return L;
-}
-template <int N> constexpr void finish(ProgB<N> &P)
-{
-    long off = 0;
-    for (int i = 0; i < N; ++i) {
-        P.layer[i].stream_off = off;
-        P.layer[i].chunk_hw = pick_GX(P.layer[i].KB32, P.layer[i].NT32) * P.layer[i].KB32 * 2048;
-        off += (long)P.layer[i].NT32 * P.layer[i].KB32 * 2048;
-    }
-    P.stream_hw = off;
-}
-constexpr ProgB<R_COUNT> make_rad()
-{
-    ProgB<R_COUNT> P{};
-    const FlatOffsets::Lvl &c = kFlat.lvl[0], &n = kFlat.lvl[1];
-    auto sq = [](long w0, long w1, int ld, int krows) { return SegB{{w0, w1}, ld, 0, krows, (krows + 31) / 32}; };
-    LayerB *L = P.layer;
-    // colour branch, from its head back (modules.py:276-287)
-    L[R_RGBH] = mkb(4, SegB{{c.rgb_w, n.rgb_w}, BR_H, 0, 3, 2}, RowB{BR_H, 0, BR_H});
-    L[R_D3] = mkb(4, sq(c.dir_w[3], n.dir_w[3], BR_H, BR_H), RowB{BR_H, 0, BR_H});
-    L[R_D2] = mkb(4, sq(c.dir_w[2], n.dir_w[2], BR_H, BR_H), RowB{BR_H, 0, BR_H});
-    L[R_D1] = mkb(4, sq(c.dir_w[1], n.dir_w[1], BR_H, BR_H), RowB{BR_H, 0, BR_H});
-    L[R_GRIDF] = mkb(2, sq(c.dir_w[0], n.dir_w[0], D_DIR_IN, BR_H), RowB{D_GRID, TR_H + D_DIR, D_GRID});       // d grid features (tile 1: padding)
-    // seg branch (modules.py:289-294)
-    L[R_SEGH] = mkb(4, SegB{{c.segout_w, n.segout_w}, BR_H, 3, N_SEG, 2}, RowB{BR_H, 0, BR_H});
-    L[R_S3] = mkb(4, sq(c.seg_w[3], n.seg_w[3], BR_H, BR_H), RowB{BR_H, 0, BR_H});
-    L[R_S2] = mkb(4, sq(c.seg_w[2], n.seg_w[2], BR_H, BR_H), RowB{BR_H, 0, BR_H});
-    L[R_S1] = mkb(4, sq(c.seg_w[1], n.seg_w[1], BR_H, BR_H), RowB{BR_H, 0, BR_H});
-    // d feat = W_S0^T dS0 + W_D0[:, :256]^T dC0 + w_alpha dsigma
-    L[R_FEATIN] = mkb(8, sq(c.seg_w[0], n.seg_w[0], TR_H, BR_H), RowB{TR_H, 0, TR_H}, sq(c.dir_w[0], n.dir_w[0], D_DIR_IN, BR_H),
-                      SegB{{c.alpha_w, n.alpha_w}, TR_H, 15, 1, 1});
-    // trunk (modules.py:267-274), skip layer 3: [h | PE(x') | PE(w) | pose]
-    L[R_FEAT] = mkb(8, sq(c.feat_w, n.feat_w, TR_H, TR_H), RowB{TR_H, 0, TR_H});
-#if SAHS_MODEL == 0
-    for (int i = 7; i >= 4; --i) L[R_T7 + (7 - i)] = mkb(8, sq(c.xyz_w[i], n.xyz_w[i], TR_H, TR_H), RowB{TR_H, 0, TR_H});
-#endif
+static_assert(!USE_DEFORM || DIN_LD == 96 || DIN_LD == 128, "the encodings' rows are one 32-row tile short of or exactly the layer's 4 tiles");
 #if SAHS_MODEL != 2
-    L[R_T3IN] = mkb(4, sq(c.xyz_w[3], n.xyz_w[3], TR_H + D_TR_IN, TR_H), RowB{16 * KB_XYZ, TR_H, D_XYZ}, SegB{{0, 0}, 0, 0, 0, 0}, SegB{{0, 0}, 0, 0, 0, 0},
-                    RowB{16 * KB_AMB, TR_H + D_XYZ, D_AMB});                                                      // d [PE(x') | PE(w)] (audio: tile 3 is padding)
-#endif
-    L[R_T3] = mkb(8, sq(c.xyz_w[3], n.xyz_w[3], TR_H + D_TR_IN, TR_H), RowB{TR_H, 0, TR_H});
-    L[R_T2] = mkb(8, sq(c.xyz_w[2], n.xyz_w[2], TR_H, TR_H), RowB{TR_H, 0, TR_H});
-    L[R_T1] = mkb(8, sq(c.xyz_w[1], n.xyz_w[1], TR_H, TR_H), RowB{TR_H, 0, TR_H});
-#if SAHS_MODEL != 2
-    L[R_T0IN] = mkb(4, sq(c.xyz_w[0], n.xyz_w[0], D_TR_IN, TR_H), RowB{16 * KB_XYZ, 0, D_XYZ}, SegB{{0, 0}, 0, 0, 0, 0}, SegB{{0, 0}, 0, 0, 0, 0},
-                    RowB{16 * KB_AMB, D_XYZ, D_AMB});
-#endif
-    finish(P);
-    return P;
-}
-#if SAHS_MODEL != 2
-constexpr ProgB<D_COUNT> make_def()
-{
-    ProgB<D_COUNT> P{};
-    const FlatOffsets &f = kFlat;
-    auto sq = [](long w, int ld, int krows) { return SegB{{w, w}, ld, 0, krows, (krows + 31) / 32}; };
-    LayerB *L = P.layer;
-    // hyper sheet (modules.py:444-462): w = fc_ambient(g5); skip layer 4: [g | PE(x) | driving | pose]
-    L[D_HF] = mkb(2, SegB{{f.hyp_fw, f.hyp_fw}, HYP_H, 0, AMB_DIM, 2}, RowB{HYP_H, 0, HYP_H});
-    L[D_H5] = mkb(2, sq(f.hyp_w[5], HYP_H, HYP_H), RowB{HYP_H, 0, HYP_H});
-    L[D_H4] = mkb(2, sq(f.hyp_w[4], HYP_H + D_DEF_IN, HYP_H), RowB{HYP_H, 0, HYP_H});
-    L[D_H3] = mkb(2, sq(f.hyp_w[3], HYP_H, HYP_H), RowB{HYP_H, 0, HYP_H});
-    L[D_H2] = mkb(2, sq(f.hyp_w[2], HYP_H, HYP_H), RowB{HYP_H, 0, HYP_H});
-    L[D_H1] = mkb(2, sq(f.hyp_w[1], HYP_H, HYP_H), RowB{HYP_H, 0, HYP_H});
-    // warp field (modules.py:371-390): dx = tanh(fc_final(h5))
-    L[D_WF] = mkb(4, SegB{{f.warp_fw, f.warp_fw}, WARP_H, 0, 3, 2}, RowB{WARP_H, 0, WARP_H});
-    L[D_W5] = mkb(4, sq(f.warp_w[5], WARP_H, WARP_H), RowB{WARP_H, 0, WARP_H});
-    L[D_W4] = mkb(4, sq(f.warp_w[4], WARP_H + D_DEF_IN, WARP_H), RowB{WARP_H, 0, WARP_H});
-    L[D_W3] = mkb(4, sq(f.warp_w[3], WARP_H, WARP_H), RowB{WARP_H, 0, WARP_H});
-    L[D_W2] = mkb(4, sq(f.warp_w[2], WARP_H, WARP_H), RowB{WARP_H, 0, WARP_H});
-    L[D_W1] = mkb(4, sq(f.warp_w[1], WARP_H, WARP_H), RowB{WARP_H, 0, WARP_H});
-    finish(P);
-    return P;
-}
-constexpr ProgB<D_COUNT> kDef = make_def();
-__device__ const ProgB<D_COUNT> dDef = make_def();
-constexpr long DEF_HW = kDef.stream_hw;      // halfwords of the deformation stream
+constexpr bwp::Prog<D_COUNT> kDef = bwp::make_def<32, D_COUNT>(pick_GX);
+__device__ const bwp::Prog<D_COUNT> dDef = kDef;
+static_assert(kDef.n == D_COUNT, "DefLayer names every layer of the program");
+constexpr long DEF_HW = kDef.stream;         // halfwords of the deformation stream
 #else
 constexpr long DEF_HW = 0;                   // (no deformation nets)
 #endif
-constexpr ProgB<R_COUNT> kRad = make_rad();
-__device__ const ProgB<R_COUNT> dRad = make_rad();
-constexpr long RAD_HW = kRad.stream_hw;      // halfwords of a level's radiance stream
+constexpr bwp::Prog<R_COUNT> kRad = bwp::make_rad<32, R_COUNT>(pick_GX);
+__device__ const bwp::Prog<R_COUNT> dRad = kRad;
+static_assert(kRad.n == R_COUNT, "RadLayer names every layer of the program");
+constexpr long RAD_HW = kRad.stream;         // halfwords of a level's radiance stream
 static_assert(RAD_HW % 8 == 0 && DEF_HW % 8 == 0, "16-byte granules");
 
 // ---- transposed, split stream of one part: [layer][tile32][k-step][hi 64 x 8 | lo 64 x 8]; lane 32 h + i of k-step (block b, step st)
 // holds A[32 t + i][32 b + 16 st + 8 (j >> 2) + 4 h + (j & 3)], j = 0..7 (the B-operand order of bf16x3_pipe.hpp) -----------------------
 template <int N>
-__device__ __forceinline__ void pack_one(const ProgB<N> &Pg, const float *__restrict__ flat, unsigned short *__restrict__ out, int level, long e)
+__device__ __forceinline__ void pack_one(const bwp::Prog<N> &Pg, const float *__restrict__ flat, unsigned short *__restrict__ out, int level, long e)
 {
     const long hw = e * 16;                                // one thread: the hi AND lo fragment granule of one lane (2 x 8 halfwords)
-    int li = 0;
-    while (li + 1 < N && Pg.layer[li + 1].stream_off <= hw) ++li;
-    const LayerB &L = Pg.layer[li];
+    const bwp::BLayer &L = bwp::layer_at(Pg, hw);
     const long w = hw - L.stream_off;
-    const int per_tile = L.KB32 * 2048;
+    const int per_tile = L.KB * 2048;
     const int t = (int)(w / per_tile);
     const int rem = (int)(w - (long)t * per_tile);
     const int f = rem >> 10, lane = (rem & 1023) >> 4;     // fragment pair f = 2 b + st; 16 halfwords (hi 8 + lo 8) per lane and pair
     const int b = f >> 1, st = f & 1, i = lane & 31, h = lane >> 5;
-    const int row = 32 * t + i;
-    int col = -1, r0 = 0;
-    for (int rs = 0; rs < L.nrow; ++rs) {
-        if (row >= r0 && row < r0 + L.row[rs].rows) { if (row - r0 < L.row[rs].valid) col = L.row[rs].col0 + (row - r0); break; }
-        r0 += L.row[rs].rows;
-    }
-    int bb = b, sg = -1;
-    for (int s = 0; s < L.nseg; ++s) {
-        if (bb < L.seg[s].blocks) { sg = s; break; }
-        bb -= L.seg[s].blocks;
-    }
+    const bwp::Spot at = bwp::spot<32>(L, level, 32 * t + i, b);
     unsigned short vh[8], vl[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int c = 32 * bb + 16 * st + 8 * (j >> 2) + 4 * h + (j & 3);
-        float x = 0.0f;
-        if (sg >= 0 && col >= 0) {
-            const int k = c - L.seg[sg].kshift;
-            if (k >= 0 && k < L.seg[sg].krows) x = flat[L.seg[sg].w_off[level] + (long)k * L.seg[sg].ld + col];
-        }
+        const long src = bwp::element(at, 16 * st + 8 * (j >> 2) + 4 * h + (j & 3));
+        const float x = src >= 0 ? flat[src] : 0.0f;
         const __bf16 hi = (__bf16)x;
         vh[j] = __builtin_bit_cast(unsigned short, hi);
         vl[j] = __builtin_bit_cast(unsigned short, (__bf16)(x - (float)hi));
@@ -301,13 +191,13 @@ __device__ __forceinline__ void flush_x(St &st, const PEP pep)
     fence();
 }
 
-constexpr int BWC_ZERO_BYTES_ = 2048;
-constexpr int BWC_STAGE_OFF_ = LDS_BIAS_BYTE_OFF + BWC_ZERO_BYTES_;
+constexpr int BWC_ZERO_BYTES = 2048;                                       // the "bias" of every backward layer: zeros
+constexpr int BWC_STAGE_BYTE_OFF = LDS_BIAS_BYTE_OFF + BWC_ZERO_BYTES;     // staging tiles behind the zero bias page
 // this lane's part in staging its wave's tiles (StageCtx): the wave's 32 samples are consecutive, p0 = 128 tile + 32 wave
 __device__ __forceinline__ StageCtx make_stage(const char *lds, int wave, int lane, long tile, long P)
 {
     StageCtx sc;
-    const uint32_t base = lds_addr_of(lds) + BWC_STAGE_OFF_ + (uint32_t)wave * STAGE_WAVE_BYTES;
+    const uint32_t base = lds_addr_of(lds) + BWC_STAGE_BYTE_OFF + (uint32_t)wave * STAGE_WAVE_BYTES;
     sc.wr = base + (uint32_t)(lane & 31) * STAGE_ROW_BYTES + 16u * (lane >> 5);
     sc.rd = base + (uint32_t)(lane >> 3) * STAGE_ROW_BYTES + 16u * (lane & 7);
     sc.pc = 16u * (lane & 7);
@@ -318,9 +208,6 @@ __device__ __forceinline__ StageCtx make_stage(const char *lds, int wave, int la
     return sc;
 }
 
-constexpr int BWC_ZERO_BYTES = 2048;                                       // the "bias" of every backward layer: zeros
-constexpr int BWC_STAGE_BYTE_OFF = LDS_BIAS_BYTE_OFF + BWC_ZERO_BYTES;
-static_assert(BWC_STAGE_BYTE_OFF == BWC_STAGE_OFF_, "staging tiles behind the zero bias page");
 constexpr int BWC_LDS_BYTES = BWC_STAGE_BYTE_OFF + (X_THREADS / WAVE) * STAGE_WAVE_BYTES;
 static_assert(BWC_LDS_BYTES <= 160 * 1024, "LDS budget");
 
@@ -343,8 +230,8 @@ __device__ __forceinline__ void zero_block(Blk &o)
     o.s[0] = o.s[1] = o.l[0] = o.l[1] = u32x4{0u, 0u, 0u, 0u};
 }
 
-#define CHR(id) (kRad.layer[id].chunk_hw)
-#define CHD(id) (kDef.layer[id].chunk_hw)
+#define CHR(id) (kRad.layer[id].chunk)
+#define CHD(id) (kDef.layer[id].chunk)
 
 // Radiance nets of one level, backwards.  d_raw (P,16); bits: the radiance sign planes (sbits::BR_*); dact: plane c of the act:: table at
 // dact + c * P (written: C, S, FEAT, T planes); dgridf (P,32); din_a, din_b (P,96): the encodings' gradient through the skip layer and
@@ -485,7 +372,7 @@ field_backward_chain_rad_kernel(const unsigned short *__restrict__ stream, long 
             auto e3 = ep256(sbits::BR_T + 8 * 3, act::T + 3 * 256);
             dense_x<4, 4, 1, 8, CHR(R_FEAT), true, 3>(cx, st, dS0, dC0, draw, F, 0, ef, es0);
             dense_x<8, 0, 0, 8, CHR(R_T3IN), true, 7>(cx, st, F, nullptr, nullptr, G, 0, e3, ef);      // G = dT3 (last tile pending)
-            BwdEp<false, DIN_W / 32, DIN_W> ea;
+            BwdEp<false, DIN_LD / 32, DIN_LD> ea;
             ea.slope = 1.0f; ea.base = din_a; ea.sc = sc;
             {
                 Blk dummy[4];
@@ -498,7 +385,7 @@ field_backward_chain_rad_kernel(const unsigned short *__restrict__ stream, long 
             auto e0 = ep256(sbits::BR_T + 0, act::T + 0);
             dense_x<8, 0, 0, 8, CHR(R_T1), true, 7>(cx, st, F, nullptr, nullptr, G, 0, e1, e2);
             dense_x<8, 0, 0, 8, CHR(R_T0IN), true, 7>(cx, st, G, nullptr, nullptr, F, 0, e0, e1);      // F = dT0
-            BwdEp<false, DIN_W / 32, DIN_W> eb;
+            BwdEp<false, DIN_LD / 32, DIN_LD> eb;
             eb.slope = 1.0f; eb.base = din_b; eb.sc = sc;
             {
                 Blk dummy[4];

@@ -7,31 +7,22 @@
 // tile of a layer (lane (q, j): gradients 4q..4q+3 of sample j) is the B operand of the next, the transposed weights stream L2 -> LDS by
 // LDS-DMA in <= 32 KB chunks.  The epilogue policy is the backward's: start from zero, multiply by the (leaky-)ReLU derivative read from
 // the sign bits the saving forward wrote (sahs_layout.hpp: sbits -- the forward's lane (q, j) wrote the very word this lane (q, j) reads),
-// store the dZ tile into the plane of its layer (the operand of the weight-gradient launch, field_bwd.hip: gemm_tn_jobs*_f32_kernel).
+// store the dZ tile into the plane of its layer (the operand of the weight-gradient launch, field_bwd_gemm.hip: gemm_tn_jobs*_f32_kernel).
 // Same planes, seam buffers and launch order as the split-operand chain; sums in a different order than the per-layer GEMMs it replaces
-// (gemm_dma_kernel<false, false>), same exact products.  Built once per model, with the trunk and the parts of field_bwd_chain.hip's programs.
+// (gemm_dma_kernel<false, false>), same exact products.  Built once per model, from the same layer table as field_bwd_chain.hip's programs (bwd_program.hpp).
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
 #include "sahs_launchers.hpp"
 #include "sahs_layout.hpp"
+#include "bwd_program.hpp"
 #include "f32_pipe.hpp"
 
 namespace SAHS_NS {
 namespace bwf {
 
-// ---- the backward layer program, in 16-row tiles and 16-gradient k-blocks ------------------------------------------------------------
-// A backward layer multiplies A = (part of) W^T: output row = an INPUT feature of the forward layer (W's column col0 + row), K index = an
-// OUTPUT feature of the forward layer (W's row k - kshift).  Up to two K segments (d feat sums the seg and colour branches), up to two row
-// ranges (the encodings' gradient: PE(x') columns, then PE(w) columns).  The heads take the 16-float d_raw row [drgb3 | dseg12 | dsigma]
-// as their one k-block: kshift places the head's weight rows (fc_seg: k = 3..14, fc_alpha: k = 15).
-struct SegF { long w_off[2]; int ld, kshift, krows; };
-struct RowF { int rows, col0, valid; };
-struct LayerF {
-    int NT, KB, nseg; SegF seg[2]; int blocks[2];
-    int nrow; RowF row[2];
-    long stream_off;      // floats, in this part's stream
-    int chunk;            // floats per LDS chunk
-};
+// ---- the backward layer program: bwd_program.hpp's, in 16-row tiles and 16-gradient k-blocks (floats), chunked as dense_ep streams it.
+// The enums name its layers in the order of bwp::make_rad / make_def = the order of the stream = the order in which the kernels below walk
+// it.  The heads take the 16-float d_raw row [drgb3 | dseg12 | dsigma] as their one k-block -------------------------------------------
 #if SAHS_MODEL == 0
 enum RadF { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATA, R_FEATB, R_FEAT, R_T7, R_T6, R_T5, R_T4, R_T3IN, R_T3, R_T2, R_T1,
             R_T0IN, R_COUNT };
@@ -40,120 +31,36 @@ enum RadF { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATA
 #else
 enum RadF { R_RGBH, R_D3, R_D2, R_D1, R_GRIDF, R_SEGH, R_S3, R_S2, R_S1, R_FEATA, R_FEATB, R_FEAT, R_T3, R_T2, R_T1, R_COUNT };      // (no encodings' rows: field_bwd_chain.hip)
 #endif
-constexpr int DIN_W = 16 * (KB_XYZ + KB_AMB);      // a row of the encodings' gradient (din_a, din_b): 96 | 128 floats (SAHS_MODEL 0 | 1)
 enum DefF { D_HF, D_H5, D_H4, D_H3, D_H2, D_H1, D_WF, D_W5, D_W4, D_W3, D_W2, D_W1, D_COUNT };
-template <int N> struct ProgF { LayerF layer[N]; long stream_floats; };
-
-constexpr LayerF mkf(SegF s0, RowF r0, SegF s1 = {{0, 0}, 0, 0, 0}, RowF r1 = {0, 0, 0})
-{
-    LayerF L{};
-    L.seg[0] = s0; L.seg[1] = s1;
-    L.nseg = 1 + (s1.krows > 0);
-    L.blocks[0] = (s0.kshift + s0.krows + 15) / 16;
-    L.blocks[1] = (s1.kshift + s1.krows + 15) / 16;
-    L.KB = L.blocks[0] + L.blocks[1];
-    L.row[0] = r0; L.row[1] = r1;
-    L.nrow = 1 + (r1.rows > 0);
-    L.NT = (r0.rows + r1.rows) / 16;
-    return L;
-}
-template <int N> constexpr void finish(ProgF<N> &P)
-{
-    long off = 0;
-    for (int i = 0; i < N; ++i) {
-        P.layer[i].stream_off = off;
-        P.layer[i].chunk = pick_G(P.layer[i].KB, P.layer[i].NT) * P.layer[i].KB * 256;
-        off += (long)P.layer[i].NT * P.layer[i].KB * 256;
-    }
-    P.stream_floats = off;
-}
-constexpr ProgF<R_COUNT> make_rad()
-{
-    ProgF<R_COUNT> P{};
-    const FlatOffsets::Lvl &c = kFlat.lvl[0], &n = kFlat.lvl[1];
-    auto sq = [](long w0, long w1, int ld, int krows) { return SegF{{w0, w1}, ld, 0, krows}; };
-    LayerF *L = P.layer;
-    // colour branch, from its head back (modules.py:276-287)
-    L[R_RGBH] = mkf(SegF{{c.rgb_w, n.rgb_w}, BR_H, 0, 3}, RowF{BR_H, 0, BR_H});
-    for (int i = 3; i >= 1; --i) L[R_D3 + (3 - i)] = mkf(sq(c.dir_w[i], n.dir_w[i], BR_H, BR_H), RowF{BR_H, 0, BR_H});
-    L[R_GRIDF] = mkf(sq(c.dir_w[0], n.dir_w[0], D_DIR_IN, BR_H), RowF{D_GRID, TR_H + D_DIR, D_GRID});
-    // seg branch (modules.py:289-294)
-    L[R_SEGH] = mkf(SegF{{c.segout_w, n.segout_w}, BR_H, 3, N_SEG}, RowF{BR_H, 0, BR_H});
-    for (int i = 3; i >= 1; --i) L[R_S3 + (3 - i)] = mkf(sq(c.seg_w[i], n.seg_w[i], BR_H, BR_H), RowF{BR_H, 0, BR_H});
-    // d feat = w_alpha dsigma (A) + W_S0^T dS0 + W_D0[:, :256]^T dC0 (B, accumulating)
-    L[R_FEATA] = mkf(SegF{{c.alpha_w, n.alpha_w}, TR_H, 15, 1}, RowF{TR_H, 0, TR_H});
-    L[R_FEATB] = mkf(sq(c.seg_w[0], n.seg_w[0], TR_H, BR_H), RowF{TR_H, 0, TR_H}, sq(c.dir_w[0], n.dir_w[0], D_DIR_IN, BR_H));
-    // trunk (modules.py:267-274), skip layer 3: [h | PE(x') | PE(w) | pose]
-    L[R_FEAT] = mkf(sq(c.feat_w, n.feat_w, TR_H, TR_H), RowF{TR_H, 0, TR_H});
-#if SAHS_MODEL == 0
-    for (int i = 7; i >= 4; --i) L[R_T7 + (7 - i)] = mkf(sq(c.xyz_w[i], n.xyz_w[i], TR_H, TR_H), RowF{TR_H, 0, TR_H});
-#endif
 #if SAHS_MODEL != 2
-    L[R_T3IN] = mkf(sq(c.xyz_w[3], n.xyz_w[3], TR_H + D_TR_IN, TR_H), RowF{16 * KB_XYZ, TR_H, D_XYZ}, SegF{{0, 0}, 0, 0, 0},
-                    RowF{16 * KB_AMB, TR_H + D_XYZ, D_AMB});
-#endif
-    L[R_T3] = mkf(sq(c.xyz_w[3], n.xyz_w[3], TR_H + D_TR_IN, TR_H), RowF{TR_H, 0, TR_H});
-    L[R_T2] = mkf(sq(c.xyz_w[2], n.xyz_w[2], TR_H, TR_H), RowF{TR_H, 0, TR_H});
-    L[R_T1] = mkf(sq(c.xyz_w[1], n.xyz_w[1], TR_H, TR_H), RowF{TR_H, 0, TR_H});
-#if SAHS_MODEL != 2
-    L[R_T0IN] = mkf(sq(c.xyz_w[0], n.xyz_w[0], D_TR_IN, TR_H), RowF{16 * KB_XYZ, 0, D_XYZ}, SegF{{0, 0}, 0, 0, 0}, RowF{16 * KB_AMB, D_XYZ, D_AMB});
-#endif
-    finish(P);
-    return P;
-}
-#if SAHS_MODEL != 2
-constexpr ProgF<D_COUNT> make_def()
-{
-    ProgF<D_COUNT> P{};
-    const FlatOffsets &f = kFlat;
-    auto sq = [](long w, int ld, int krows) { return SegF{{w, w}, ld, 0, krows}; };
-    LayerF *L = P.layer;
-    // hyper sheet (modules.py:444-462): w = fc_ambient(g5); skip layer 4: [g | PE(x) | driving | pose]
-    L[D_HF] = mkf(sq(f.hyp_fw, HYP_H, AMB_DIM), RowF{HYP_H, 0, HYP_H});
-    for (int i = 5; i >= 1; --i) L[D_H5 + (5 - i)] = mkf(sq(f.hyp_w[i], i == 4 ? HYP_H + D_DEF_IN : HYP_H, HYP_H), RowF{HYP_H, 0, HYP_H});
-    // warp field (modules.py:371-390): dx = tanh(fc_final(h5))
-    L[D_WF] = mkf(sq(f.warp_fw, WARP_H, 3), RowF{WARP_H, 0, WARP_H});
-    for (int i = 5; i >= 1; --i) L[D_W5 + (5 - i)] = mkf(sq(f.warp_w[i], i == 4 ? WARP_H + D_DEF_IN : WARP_H, WARP_H), RowF{WARP_H, 0, WARP_H});
-    finish(P);
-    return P;
-}
-constexpr ProgF<D_COUNT> kDef = make_def();
-__device__ const ProgF<D_COUNT> dDef = make_def();
-constexpr long DEF_FLOATS = kDef.stream_floats;
+constexpr bwp::Prog<D_COUNT> kDef = bwp::make_def<16, D_COUNT>(pick_G);
+__device__ const bwp::Prog<D_COUNT> dDef = kDef;
+static_assert(kDef.n == D_COUNT, "DefF names every layer of the program");
+constexpr long DEF_FLOATS = kDef.stream;
 static_assert(kDef.layer[D_W1].chunk >= PIECE_FLOATS, "the stream's last chunk is whole DMA pieces");
 #else
 constexpr long DEF_FLOATS = 0;      // (no deformation nets)
 #endif
-constexpr ProgF<R_COUNT> kRad = make_rad();
-__device__ const ProgF<R_COUNT> dRad = make_rad();
-constexpr long RAD_FLOATS = kRad.stream_floats;
+constexpr bwp::Prog<R_COUNT> kRad = bwp::make_rad<16, R_COUNT>(pick_G);
+__device__ const bwp::Prog<R_COUNT> dRad = kRad;
+static_assert(kRad.n == R_COUNT, "RadF names every layer of the program");
+constexpr long RAD_FLOATS = kRad.stream;
 // (a DMA piece is 8 KB: a chunk shorter than that is over-read into what follows it in the stream -- never past the stream's end)
 static_assert(kRad.layer[R_COUNT - 1].chunk >= PIECE_FLOATS, "the stream's last chunk is whole DMA pieces");
 
 // ---- transposed stream of one part: [layer][tile16][k-block][lane 64][4]; lane = 16 q + i holds A[16 t + i][16 b + 4 q + r], r = 0..3 (the
 // A-fragment order of f32_pipe.hpp, as pack.hip writes the forward's) ----------------------------------------------------------------------
 template <int N>
-__device__ __forceinline__ float pack_one(const ProgF<N> &Pg, const float *__restrict__ flat, int level, long e)
+__device__ __forceinline__ float pack_one(const bwp::Prog<N> &Pg, const float *__restrict__ flat, int level, long e)
 {
-    int li = 0;
-    while (li + 1 < N && Pg.layer[li + 1].stream_off <= e) ++li;
-    const LayerF &L = Pg.layer[li];
+    const bwp::BLayer &L = bwp::layer_at(Pg, e);
     const long w = e - L.stream_off;
     const int per_tile = L.KB * 256;
     const int t = (int)(w / per_tile);
     const int rem = (int)(w - (long)t * per_tile);
     const int b = rem >> 8, lane = (rem & 255) >> 2, r = rem & 3;
-    const int row = 16 * t + (lane & 15), q = lane >> 4;
-    int col = -1, r0 = 0;
-    for (int rs = 0; rs < L.nrow; ++rs) {
-        if (row < r0 + L.row[rs].rows) { if (row - r0 < L.row[rs].valid) col = L.row[rs].col0 + (row - r0); break; }
-        r0 += L.row[rs].rows;
-    }
-    int bb = b, sg = 0;
-    if (bb >= L.blocks[0]) { bb -= L.blocks[0]; sg = 1; }
-    const int k = 16 * bb + 4 * q + r - L.seg[sg].kshift;
-    if (col < 0 || k < 0 || k >= L.seg[sg].krows) return 0.0f;
-    return flat[L.seg[sg].w_off[level] + (long)k * L.seg[sg].ld + col];
+    const long src = bwp::element(bwp::spot<16>(L, level, 16 * t + (lane & 15), b), 4 * (lane >> 4) + r);
+    return src >= 0 ? flat[src] : 0.0f;
 }
 __global__ void __launch_bounds__(256) pack_bwd_stream_f32_kernel(const float *__restrict__ flat, float *__restrict__ out, int level, int part)
 {
@@ -338,9 +245,9 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
             auto e3 = ep256(3, act::T + 3 * 256);
             dense_ep<16, 0, 16, CHR(R_T3IN)>(cx, F, nullptr, G, e3);
             {
-                BwdEpF<false> ei{false, 1.0f, {0u, 0u}, din_a + p * DIN_W + 4 * q};
-                f32x4 dn[DIN_W / 16];
-                dense_ep<16, 0, DIN_W / 16, CHR(R_T3)>(cx, G, nullptr, dn, ei);
+                BwdEpF<false> ei{false, 1.0f, {0u, 0u}, din_a + p * DIN_LD + 4 * q};
+                f32x4 dn[DIN_LD / 16];
+                dense_ep<16, 0, DIN_LD / 16, CHR(R_T3)>(cx, G, nullptr, dn, ei);
             }
 #pragma unroll 1
             for (int l = 2; l >= 0; --l) {             // layers T3, T2, T1 (next chunks: T2, T1, T0IN, all 32 KB) leave dT2..dT0
@@ -351,9 +258,9 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
             }
             static_assert(CHR(R_T2) == CHR(R_T1) && CHR(R_T2) == CHR(R_T0IN), "rolled trunk layers");
             {
-                BwdEpF<false> ei{false, 1.0f, {0u, 0u}, din_b + p * DIN_W + 4 * q};
-                f32x4 dn[DIN_W / 16];
-                dense_ep<16, 0, DIN_W / 16, CHR(R_RGBH)>(cx, G, nullptr, dn, ei);
+                BwdEpF<false> ei{false, 1.0f, {0u, 0u}, din_b + p * DIN_LD + 4 * q};
+                f32x4 dn[DIN_LD / 16];
+                dense_ep<16, 0, DIN_LD / 16, CHR(R_RGBH)>(cx, G, nullptr, dn, ei);
             }
         }
 #else
@@ -374,7 +281,7 @@ field_backward_chain_rad_f32_kernel(const float *__restrict__ stream, long P, co
 #undef DZ
     }
 }
-static_assert(SAHS_MODEL != 0 || DIN_W == 96, "the encodings' gradient rows (din_a, din_b) are 96 floats");
+static_assert(SAHS_MODEL != 0 || DIN_LD == 96, "the encodings' gradient rows (din_a, din_b) are 96 floats");
 
 #if SAHS_MODEL != 2
 

@@ -8,7 +8,11 @@
 // single source of truth for that program: which state_dict tensor feeds each layer, how its
 // columns map onto 16-feature k-blocks, where its bias lives, and how it is cut into the LDS
 // chunks the kernel streams.  pack.hip (weight packer, conditioning fold) and field_*.hip are
-// all generated from this table, so they cannot disagree.
+// all generated from this table, so they cannot disagree.  So is the fused backward: bwd_program.hpp
+// turns this table into the transposed layer programs of the data-gradient chains
+// (field_bwd_chain.hip, field_bwd_chain_f32.hip), the lookup of their stream packers and the job
+// tables of the weight-gradient launch (field_bwd.hip) -- only the per-layer walk of field_bwd.hip
+// states the network a second time, on purpose (it is what the tests compare the fused walk with).
 //
 // Per-frame constants (driving[76] from AudioNet, pose36) are NOT network inputs here: the
 // reference concatenates them to every point (models.py:518,521); we fold W[:, const]*c into the
@@ -429,7 +433,7 @@ constexpr int STRIDE = S + 4 * 128;     // sum of the array widths; AudioFaceMod
 
 // =============================================================================================
 // Sign-bit planes (round 4): field_forward_f32_kernel<SAVE> also writes, for every (leaky-)ReLU layer, which of its outputs are > 0 --
-// the derivative mask of the backward chain (field_bwd_fused.hip), 1 bit instead of the 32 of the saved activation.  One plane per
+// the derivative mask of the backward chains (field_bwd_chain.hip, field_bwd_chain_f32.hip), 1 bit instead of the 32 of the saved activation.  One plane per
 // layer, [P][4 q][NW] 32-bit words: the lane that holds features 16 t + 4 q + r (r = 0..3) of every 16-row tile t of its sample sets
 // bit 4 t + r of ITS OWN word(s) -- no cross-lane work in the forward; NW = NT / 8 words (at least 1).  The chain kernel's lane
 // (sample, h) reads words q = h and q = 2 + h: its 16 values of 32-row tile T are features 32 T + 8 g + 4 h + i, i.e. 16-row tile
