@@ -153,6 +153,40 @@ struct SparseArgs {
     int has_bg;              // a background prior replaces the last sample's channels
 };
 constexpr long SPARSE_HEAD_BYTES = 256, SPARSE_RECORD_BYTES = 16 + 16 * 16 * 4;
+// Timing-only switches of the sparse instances (tools/ablate.py; results are WRONG by construction, the shipped library has none of them):
+// what a tile's encodings, its prologue loads and its record append cost beside the MFMA layers.
+#if defined(SAHS_DIAG) && defined(SAHS_F32_ENC2)
+constexpr bool DIAG_ENC2 = true;             // trunk: build the encodings again before the skip layer (as the dense instances do)
+#else
+constexpr bool DIAG_ENC2 = false;
+#endif
+#if defined(SAHS_DIAG) && defined(SAHS_F32_NOENC)
+constexpr bool DIAG_NOENC = true;            // sparse instances: no sin_octave at all (a block is its lane's coordinates)
+#else
+constexpr bool DIAG_NOENC = false;
+#endif
+#if defined(SAHS_DIAG) && defined(SAHS_F32_NOLOADS_TRUNK)
+constexpr bool DIAG_NOLOADS_TRUNK = true;    // trunk: x', w (or the point) made up from the sample index instead of loaded
+#else
+constexpr bool DIAG_NOLOADS_TRUNK = false;
+#endif
+#if defined(SAHS_DIAG) && defined(SAHS_F32_NOLOADS_BRANCH)
+constexpr bool DIAG_NOLOADS_BRANCH = true;   // branch: header, raw row, feat, ray direction and grid corners made up instead of loaded
+#else
+constexpr bool DIAG_NOLOADS_BRANCH = false;
+#endif
+#if defined(SAHS_DIAG) && defined(SAHS_F32_NOAPPEND)
+constexpr bool DIAG_NOAPPEND = true;         // trunk: no record append (the branch launches then find no records)
+#else
+constexpr bool DIAG_NOAPPEND = false;
+#endif
+// (diag) a cheap stand-in for pe_blocks: lane-dependent values the compiler cannot fold
+template <int NB>
+__device__ __forceinline__ void diag_blocks(const float *v, int q, f32x4 *out)
+{
+#pragma unroll
+    for (int b = 0; b < NB; ++b) out[b] = f32x4{v[0], v[1], v[0] * (float)(q + b), v[1] + (float)b};
+}
 template <bool SAVE, int MODE>
 __global__ void __launch_bounds__(F32_THREADS, 2)
 field_forward_f32_kernel(const float *__restrict__ packed, const float *__restrict__ frame, int level, long P, int S,
@@ -196,6 +230,13 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         P = n < sp.cap ? n : sp.cap;
     }
     const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG;
+    // FIELD_RADIANCE_TRUNK: the x', w row of the workgroup's NEXT tile is fetched while this one multiplies (its src entry at the start of
+    // the tile, the dependent xw row behind T2), so a tile no longer starts with two dependent trips to HBM while the matrix pipe idles.
+    // The addresses use the same P - 1 clamp; a workgroup with no next tile issues nothing.
+    constexpr bool XW_AHEAD = MODE == FIELD_RADIANCE_TRUNK && !DIAG_NOLOADS_TRUNK;
+    f32x4 nx_a = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    float nx_w1 = 0.0f;
+    int nx_src = 0;
     for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         cx.refresh();
         // (a trunk launch of the 4-layer-trunk models has no rolled layer loop, so the stream offset of every chunk is the same constant
@@ -228,7 +269,11 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
 #define SBR(b, w) (sb_on ? bits_r + (long)(b) * Psv + sb_lane * (uint32_t)((w) >= 128 ? (w) / 128 : 1) : nullptr)
         float x[3] = {0.0f, 0.0f, 0.0f};
         long smp = p;            // the sample of this lane's point: its ray is smp / S, its raw row smp
-        if constexpr (BRANCH) {  // a record: x' -> stash (w is not needed behind the trunk)
+        if constexpr ((TRUNK && DIAG_NOLOADS_TRUNK) || (BRANCH && DIAG_NOLOADS_BRANCH)) {
+            const float t = (float)(p & 1023) * (1.0f / 1024.0f);
+            x[0] = t - 0.5f; x[1] = 0.25f - t; x[2] = 0.8f - t;
+            if (q == 0 && (XW_IN || BRANCH)) { stash[0] = x[0]; stash[1] = x[1]; stash[2] = x[2]; stash[3] = t; stash[4] = -t; }
+        } else if constexpr (BRANCH) {  // a record: x' -> stash (w is not needed behind the trunk)
             const f32x4 a = sp.hdr[p];
             smp = __float_as_int(a[3]);
             if (q == 0) { stash[0] = a[0]; stash[1] = a[1]; stash[2] = a[2]; }
@@ -237,11 +282,27 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             const float z = zvals[p];
 #pragma unroll
             for (int i = 0; i < 3; ++i) x[i] = rp[i] + rp[3 + i] * z;          // train_utils.py:115
+        } else if constexpr (XW_AHEAD) {
+            if (q == 0) {
+                if (tile == (long)blockIdx.x) {      // the workgroup's first tile: nothing was fetched ahead
+                    const float *row = xw + ((p / S) * (long)xw_row + src[p]) * 8;
+                    nx_a = *reinterpret_cast<const f32x4 *>(row);
+                    nx_w1 = row[4];
+                }
+                stash[0] = nx_a[0]; stash[1] = nx_a[1]; stash[2] = nx_a[2]; stash[3] = nx_a[3]; stash[4] = nx_w1;
+            }
         } else if (q == 0) {     // (XW_IN) x', w of this sample were computed by the coarse or the deformation launch: fetch through the merge permutation
             const float *row = xw + ((p / S) * (long)xw_row + src[p]) * 8;
             const f32x4 a = *reinterpret_cast<const f32x4 *>(row);
             stash[0] = a[0]; stash[1] = a[1]; stash[2] = a[2]; stash[3] = a[3]; stash[4] = row[4];
             if (sv_on) { float *d = SVP(act::XW, 16); d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; }   // the grid backward reads x'
+        }
+        // (XW_AHEAD) this lane's sample of the workgroup's next tile
+        const bool has_next = XW_AHEAD && tile + gridDim.x < ntiles;
+        const long pn_raw = p_raw + (long)gridDim.x * F32_PTS_PER_WG;
+        const long p_next = pn_raw < P ? pn_raw : P - 1;
+        if constexpr (XW_AHEAD) {
+            if (has_next && q == 0) nx_src = src[p_next];
         }
         if constexpr (!XW_IN && !BRANCH) {
 #if SAHS_MODEL == 2
@@ -253,7 +314,8 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
 #else
         f32x4 pe_x[KB_XYZ];
         {
-            pe_blocks<3, L_XYZ, KB_XYZ>(x, q, pe_x);
+            if constexpr (TRUNK && DIAG_NOENC) diag_blocks<KB_XYZ>(x, q, pe_x);
+            else pe_blocks<3, L_XYZ, KB_XYZ>(x, q, pe_x);
             if (sv_on) {
 #pragma unroll
                 for (int b = 0; b < KB_XYZ; ++b) *reinterpret_cast<f32x4 *>(SVP(act::E, 16 * KB_XYZ) + 16 * b) = pe_x[b];
@@ -330,13 +392,57 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         // ---- radiance trunk (modules.py:254-275) ----
         f32x4 fin[1];      // FINAL tile: raw[4q..4q+3] of this lane's point
         f32x4 feat[16];
-        if constexpr (BRANCH) {      // what the trunk launch left: the FINAL tile behind fc_alpha in the raw row, feat in the record
+        if constexpr (BRANCH && DIAG_NOLOADS_BRANCH) {
+            fin[0] = f32x4{x[0], x[1], x[2], x[0]};
+#pragma unroll
+            for (int b = 0; b < 16; ++b) feat[b] = f32x4{x[0] * (float)b, x[1], x[2] + (float)q, x[0]};
+        } else if constexpr (BRANCH) {      // what the trunk launch left: the FINAL tile behind fc_alpha in the raw row, feat in the record
             fin[0] = *reinterpret_cast<const f32x4 *>(raw + smp * D_RAW + 4 * q);
             const f32x4 *rec = sp.feat + (p >> 4) * (16 * 64) + q * 16 + (p & 15);
 #pragma unroll
             for (int b = 0; b < 16; ++b) feat[b] = rec[b * 64];
         } else {
             f32x4 h[16];
+            if constexpr (TRUNK) {
+                // PE(x'), PE(w) feed T0 and, re-injected, the skip layer T3A.  The TRUNK instances stop behind fc_alpha, hold no ray direction
+                // or grid blocks and compile to about 200 VGPRs, so the 24 registers can stay live through T1, T2 and the encodings be built
+                // once per tile (a build is ~1,000 VALU instructions per wave, and all eight waves run it at the same moment, the matrix pipe
+                // idle).  Measured per launch (W512 frame, LAB_NOTES.md): -1.3 % for the fine trunk; for FIELD_ALL_TRUNK, whose tile also runs
+                // the deformation nets, the -0.8 % is below that launch's own spread, and it keeps the rebuild like the dense instances.
+                constexpr bool ENC_ONCE = MODE == FIELD_RADIANCE_TRUNK && !DIAG_ENC2;
+                f32x4 in_tr[KB_XYZ + KB_AMB];
+                auto build_enc = [&]() {
+                    const float xw[3] = {stash[0], stash[1], stash[2]}, amb[2] = {stash[3], stash[4]};
+                    if constexpr (DIAG_NOENC) {
+                        diag_blocks<KB_XYZ>(xw, q, in_tr);
+                        diag_blocks<KB_AMB>(amb, q, in_tr + KB_XYZ);
+                    } else {
+                        pe_blocks<3, L_XYZ, KB_XYZ>(xw, q, in_tr);
+#if SAHS_MODEL != 2
+                        pe_blocks<AMB_DIM, L_AMB, KB_AMB, AMB_INC>(amb, q, in_tr + KB_XYZ);
+#else
+                        (void)amb;
+#endif
+                    }
+                };
+                build_enc();
+                dense<KB_XYZ, KB_AMB, 16, CHF(L_T1)>(cx, in_tr, in_tr + KB_XYZ, h, Ly[L_T0].bias_off, false, 0.01f);
+                dense<16, 0, 16, CHF(L_T2)>(cx, h, nullptr, feat, Ly[L_T1].bias_off, false, 0.01f);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) h[i] = feat[i];
+                dense<16, 0, 16, CHF(L_T3B)>(cx, h, nullptr, feat, Ly[L_T2].bias_off, false, 0.01f);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) h[i] = feat[i];
+                if constexpr (XW_AHEAD) {
+                    if (has_next && q == 0) {
+                        const float *row = xw + ((p_next / S) * (long)xw_row + nx_src) * 8;
+                        nx_a = *reinterpret_cast<const f32x4 *>(row);
+                        nx_w1 = row[4];
+                    }
+                }
+                if constexpr (!ENC_ONCE) build_enc();
+                dense<KB_XYZ, KB_AMB, 16, CHF(L_T3A)>(cx, in_tr, in_tr + KB_XYZ, feat, Ly[L_T3B].bias_off, false, 1.0f);
+            } else {
             {
                 f32x4 in_tr[KB_XYZ + KB_AMB];
                 const float xw[3] = {stash[0], stash[1], stash[2]}, amb[2] = {stash[3], stash[4]};
@@ -362,7 +468,8 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             if (dump) dsl[7] = feat[0][0];
 #pragma unroll
             for (int i = 0; i < 16; ++i) h[i] = feat[i];
-            {   // skip layer: the re-injected encoding is rebuilt here instead of staying live (24 VGPRs) through T1, T2
+            {   // skip layer: the re-injected encoding is rebuilt here instead of staying live (24 VGPRs) through T1, T2 -- registers the dense
+                // instances (237-245 VGPRs) do not have; the fine trunk above does, and builds it once
                 f32x4 in_tr[KB_XYZ + KB_AMB];
                 const float xw[3] = {stash[0], stash[1], stash[2]}, amb[2] = {stash[3], stash[4]};
                 pe_blocks<3, L_XYZ, KB_XYZ>(xw, q, in_tr);
@@ -372,6 +479,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
                 (void)amb;
 #endif
                 dense<KB_XYZ, KB_AMB, 16, CHF(L_T3A)>(cx, in_tr, in_tr + KB_XYZ, feat, Ly[L_T3B].bias_off, false, 1.0f);
+            }
             }
 #if SAHS_MODEL == 0
             dense_sv<SAVE, 16, 0, 16, CHF(L_T4)>(cx, h, nullptr, feat, 0, true, 0.01f, SV(act::T + 768, 256), SBR(sbits::BR_T + 8 * (3), 256));
@@ -403,7 +511,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             const float sg = fin[0][3] + (sp.noise != nullptr ? sp.noise[p] : 0.0f);      // sigma: row 15 = value 3 of the q == 3 lanes
             const bool live = q == 3 && p_raw < P && (last ? sp.has_bg == 0 : sg > 0.0f);
             const uint32_t mask = (uint32_t)(__ballot(live) >> 48);      // bit j: column j of this wave's 16 samples
-            if (mask != 0u) {
+            if (!DIAG_NOAPPEND && mask != 0u) {
                 uint32_t base = 0u;
                 if (cx.lane == 0) base = atomicAdd(sp.count, (unsigned int)__popc(mask));
                 base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
@@ -423,10 +531,20 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         {
             f32x4 in_d[4];
             {
+                if constexpr (BRANCH && DIAG_NOLOADS_BRANCH) {
+                    pe_blocks<3, 4, 2>(x, q, in_d);
+                    diag_blocks<2>(x, q, in_d + 2);
+                } else if constexpr (BRANCH && DIAG_NOENC) {
+                    const float *rp = rays + (smp / S) * ray_stride;
+                    const float rd[3] = {rp[3], rp[4], rp[5]};
+                    diag_blocks<2>(rd, q, in_d);
+                    grid_blocks(grid, stash[0], stash[1], stash[2], q, in_d + 2);
+                } else {
                 const float *rp = rays + (smp / S) * ray_stride;
                 const float rd[3] = {rp[3], rp[4], rp[5]};
                 pe_blocks<3, 4, 2>(rd, q, in_d);                                  // models.py:340 (raw, un-normalised direction)
                 grid_blocks(grid, stash[0], stash[1], stash[2], q, in_d + 2);     // models.py:525
+                }
                 if (sv_on) {
 #pragma unroll
                     for (int b = 0; b < 4; ++b) *reinterpret_cast<f32x4 *>(b < 2 ? SVP(act::DIR, 32) + 16 * b : SVP(act::GRID, 32) + 16 * (b - 2)) = in_d[b];
