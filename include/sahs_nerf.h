@@ -326,8 +326,14 @@ int sahs_model_render_rays_rows(int model, const void *packed, const float *fram
  * `samples` sample evaluations in one slab.  A pass of N * S samples is cut into equal ray slabs whose samples all fit (every sample may
  * be live), so any size of at least one 128-record tile and one ray's samples works; smaller ones are refused (code 5).  No host
  * synchronisation: the branch launch reads the record count from device memory.  The launch probe sees ONE record per pass, of the dense
- * launch's kind and sample count. */
+ * launch's kind and sample count.
+ * A workspace that holds the record rings of the one-launch form -- sahs_model_render_sparse_fused_workspace_bytes(model, samples) bytes
+ * on the current device: at most 512 slots per compute unit, never more than sahs_model_render_sparse_workspace_bytes(model, samples) --
+ * takes each pass in ONE launch instead: every persistent workgroup appends its live samples to a private ring and runs the branch layers
+ * itself whenever the ring holds a tile's worth.  Same results, bit for bit.  The first two 32-bit words of the workspace afterwards hold
+ * the live records of the last launch that appended (fused: the whole pass; slabs: the last slab) and 1 / 0 for fused / slabs. */
 size_t sahs_model_render_sparse_workspace_bytes(int model, long samples);
+size_t sahs_model_render_sparse_fused_workspace_bytes(int model, long samples);
 int sahs_model_render_rays_rows_sparse(int model, const void *packed, const float *frame, int precision, long N, const float *rays,
                                        int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand,
                                        const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f, float *raw,

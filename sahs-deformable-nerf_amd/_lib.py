@@ -51,6 +51,7 @@ SIGNATURES = {
     "sahs_model_executed_macs_part": (_L, [_I, _I, _I]),
     "sahs_model_render_rays_rows": (_I, [_I, _P, _P, _I, _L, _P, _I, _I, _I, _I, _I] + [_P] * 10 + [_I, _P, _P, _P, _P]),
     "sahs_model_render_sparse_workspace_bytes": (ctypes.c_size_t, [_I, _L]),
+    "sahs_model_render_sparse_fused_workspace_bytes": (ctypes.c_size_t, [_I, _L]),
     "sahs_model_render_rays_rows_sparse": (_I, [_I, _P, _P, _I, _L, _P, _I, _I, _I, _I, _I] + [_P] * 10 + [_I, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "sahs_resample_merge": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sahs_model_act_words_part": (_L, [_I, _I]),

@@ -309,6 +309,7 @@ struct ModelFns {
     // ... and the inference render's sparse branches: trunk launch + compacted branch launch, and the bytes of their record workspace
     decltype(&sahs_field_forward_f32_sparse_launch) f32_sparse;
     decltype(&sahs_field_f32_sparse_ws_bytes) f32_sparse_ws_bytes;
+    decltype(&sahs_field_f32_sparse_ring_slots) f32_sparse_ring_slots;      // slots the one-launch (fused) form of a pass needs
     // backward (field_bwd.hip): per-layer walk, cut at the (x', w) seam, fused walk
     long (*bwd_ws_words)(long);
     decltype(&sahs_field_backward_launch) bwd;
@@ -333,7 +334,7 @@ struct ModelFns {
         sahs_layout_executed_macs##sfx, sahs_layout_act_part_words##sfx, sahs_layout_act_part_col0##sfx, sahs_layout_bits_part_words##sfx, \
         sahs_fold_conditioning_launch##sfx, sahs_bwd_gemm_precision_state##sfx, sahs_bf16w_exact_leaky_state##sfx,                  \
         sahs_field_forward_f32_launch##sfx, sahs_field_forward_f32_split_launch##sfx, sahs_field_forward_f32_split_bits_launch##sfx, \
-        sahs_field_forward_f32_sparse_launch##sfx, sahs_field_f32_sparse_ws_bytes##sfx,                                              \
+        sahs_field_forward_f32_sparse_launch##sfx, sahs_field_f32_sparse_ws_bytes##sfx, sahs_field_f32_sparse_ring_slots##sfx,       \
         sahs_field_backward_ws_words##sfx, sahs_field_backward_launch##sfx, sahs_field_backward_split_launch##sfx,                  \
         sahs_field_backward_fused_ws_words##sfx, sahs_field_backward_fused_launch##sfx
 static const ModelFns kModels[3] = {
@@ -834,10 +835,12 @@ int sahs_model_render_rays_rows(int model, const void *packed, const float *fram
                              stream, row_ld, row_ld);
 }
 
-// ---- sparse branches (fp32 inference render): see csrc/field_f32.hip, FIELD_*_TRUNK / FIELD_BRANCH ----
-// One radiance evaluation of the render chain as trunk + branch launches over ray slabs sized to the record workspace; all slabs of the
-// pass under ONE probe record of the kind and sample count the dense launch has.  stage: 0 whole network up to fc_alpha (coarse pass, plain
-// chain's fine pass), 1 radiance trunk on x', w from xw through src.
+// ---- sparse branches (fp32 inference render): see csrc/field_f32.hip, FIELD_*_FUSED / FIELD_*_TRUNK / FIELD_BRANCH ----
+// One radiance evaluation of the render chain.  A workspace that holds the workgroups' record rings (never more than the pass's samples
+// rounded up to a tile, at most 512 slots per CU) takes the pass in ONE fused launch; a smaller one takes it as trunk + branch launches
+// over ray slabs sized to the record workspace.  Either way ONE probe record of the kind and sample count the dense launch has, and the
+// workspace's head afterwards holds [live records of the last launch that appended | 1 if that pass ran fused, 0 if it ran slabs].
+// stage: 0 whole network up to fc_alpha (coarse pass, plain chain's fine pass), 1 radiance trunk on x', w from xw through src.
 static long sparse_capacity(int model, size_t ws_bytes)      // record slots (a multiple of 128) a workspace of ws_bytes holds
 {
     const ModelFns &m = kModels[model];
@@ -851,6 +854,17 @@ static int field_forward_sparse(const char *who, int model, const float *pk, con
                                 const float *noise, int has_bg, void *ws, long cap, hipStream_t st)
 {
     const ModelFns &m = kModels[model];
+    // (a record's header holds its sample index as an int: a pass of more than 2^30 samples goes through slabs, which are at most that long)
+    if (N * S <= (1L << 30) && cap >= m.f32_sparse_ring_slots(N * S, num_cus())) {
+        int e = probed(probe_kind(model, SAHS_F32, level, part), N * S, st, [&] {
+            hipError_t he = hipMemsetAsync(ws, 0, 8, st);
+            if (he != hipSuccess) return (int)he;
+            return m.f32_sparse(pk, frame, level, stage + 3, N * S, S, rays, ray_stride, z, raw, xw, xw_row, 0, src, noise, has_bg, ws, cap, num_cus(), st);
+        });
+        if (e == -4) return fail(5, "%s: the sparse-branch launcher refused its record workspace (%ld slots for the rings of %ld samples)", who, cap, N * S);
+        if (e < 0) return fail(4, "%s: the sparse-branch launcher has no stage %d for this model", who, stage + 3);
+        return e ? hip_fail(who, e) : 0;
+    }
     const long per = cap / S;      // rays per slab in the worst case: every sample live
     if (per < 1) return fail(5, "%s: the sparse-branch workspace holds %ld records, one ray has %d samples", who, cap, S);
     const long nslab = (N + per - 1) / per, step = (N + nslab - 1) / nslab;      // equal slabs
@@ -873,6 +887,12 @@ static int field_forward_sparse(const char *who, int model, const float *pk, con
     if (e == -4) return fail(5, "%s: the sparse-branch launcher refused its record workspace (%ld slots for slabs of %ld samples)", who, cap, step * S);
     if (e < 0) return fail(4, "%s: the sparse-branch launcher has no stage %d for this model", who, stage);
     return e ? hip_fail(who, e) : 0;
+}
+
+size_t sahs_model_render_sparse_fused_workspace_bytes(int model, long samples)
+{
+    if (model < 0 || model > 2 || samples < 0 || samples > (1L << 30)) return 0;
+    return (size_t)kModels[model].f32_sparse_ws_bytes(samples > 0 ? kModels[model].f32_sparse_ring_slots(samples, num_cus()) : 0);
 }
 
 size_t sahs_model_render_sparse_workspace_bytes(int model, long samples)

@@ -141,7 +141,30 @@ __device__ __forceinline__ void grid_blocks(const float *__restrict__ grid, floa
 // FIELD_BRANCH launch then runs L_D0B..L_SEG over the records only and overwrites those samples' raw rows.  Columns of an MFMA tile are
 // independent, so a live sample's row has the bits of the one-launch evaluation whatever slot it lands in.
 //   FIELD_ALL_TRUNK = FIELD_ALL up to L_ALPHA, FIELD_RADIANCE_TRUNK = FIELD_RADIANCE up to L_ALPHA, FIELD_BRANCH = the two branches
-enum { FIELD_ALL = 0, FIELD_DEFORM = 1, FIELD_RADIANCE = 2, FIELD_ALL_TRUNK = 3, FIELD_RADIANCE_TRUNK = 4, FIELD_BRANCH = 5 };
+//
+// The fused sparse instances do both in ONE launch per pass.  Every persistent workgroup keeps a private FIFO ring of records in the
+// workspace: a tile runs the network up to L_ALPHA, appends its live samples to the ring (slots from per-wave live counts through LDS: no
+// global atomic), and -- when the ring held a tile's worth (128) at the START of the tile -- goes on through L_D0B..L_SEG over the 128
+// oldest records instead of wrapping at L_D0B.  All of those were stored during earlier tiles of the same workgroup (same CU, workgroup
+// barriers in between), so the loads are disjoint from this tile's stores.  After its last tile the workgroup drains the ring in
+// branch-only iterations (the last one partial: lanes past the count redo the last record and store nothing).
+//   FIELD_ALL_FUSED = FIELD_ALL_TRUNK + branches, FIELD_RADIANCE_FUSED = FIELD_RADIANCE_TRUNK + branches
+enum { FIELD_ALL = 0, FIELD_DEFORM = 1, FIELD_RADIANCE = 2, FIELD_ALL_TRUNK = 3, FIELD_RADIANCE_TRUNK = 4, FIELD_BRANCH = 5, FIELD_ALL_FUSED = 6,
+       FIELD_RADIANCE_FUSED = 7 };
+// Ring slots per workgroup of the fused instances.  The branch decision is taken from the count carried INTO a tile (>= 128), so that count
+// is at most 255 when a tile starts, a tile adds at most 128, and 383 slots can never overflow; a workgroup of T tiles appends at most
+// 128 T records in all.  Workgroup g's ring starts at the sum of its predecessors' slots.
+constexpr int SPARSE_RING = 512;
+static_assert(SPARSE_RING >= 255 + 128 && SPARSE_RING % 128 == 0, "a ring holds the carried count plus one tile");
+__host__ __device__ constexpr long sparse_ring_slots(long tiles) { return tiles * F32_PTS_PER_WG < SPARSE_RING ? tiles * F32_PTS_PER_WG : SPARSE_RING; }
+// slots in front of workgroup g's ring (g == grid: all of them) when `grid` workgroups share ntiles tiles (every workgroup one tile of each
+// full row of `grid` tiles, workgroups g < ntiles % grid one more)
+__host__ __device__ constexpr long sparse_ring_base(long ntiles, long grid, long g)
+{
+    const long tlo = ntiles / grid, rem = ntiles % grid;
+    return g * sparse_ring_slots(tlo) + (g < rem ? g : rem) * (sparse_ring_slots(tlo + 1) - sparse_ring_slots(tlo));
+}
+constexpr int LDS_RING_FLOATS = 16;      // fused instances: the waves' live counts of a tile, behind the stash
 // Record buffer of the sparse branches.  Records are taken in groups of 16 slots (one wave of the branch launch); a group's feat is laid
 // out [k-block 16][lane 64][4] like a weight fragment, so the branch launch loads it with whole 1-KB wave transactions.
 struct SparseArgs {
@@ -195,12 +218,13 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
                          float *__restrict__ xw, int xw_row, int xw_col0, const int *__restrict__ src, uint32_t *__restrict__ bits, SparseArgs sp)
 {
 #if SAHS_MODEL == 2
-    static_assert(MODE == FIELD_ALL || MODE == FIELD_ALL_TRUNK || MODE == FIELD_BRANCH, "this model has no deformation nets to split off");
+    static_assert(MODE == FIELD_ALL || MODE == FIELD_ALL_TRUNK || MODE == FIELD_BRANCH || MODE == FIELD_ALL_FUSED, "this model has no deformation nets to split off");
 #endif
     constexpr bool TRUNK = MODE == FIELD_ALL_TRUNK || MODE == FIELD_RADIANCE_TRUNK;      // stops behind L_ALPHA and appends the live samples' records
     constexpr bool BRANCH = MODE == FIELD_BRANCH;                                        // walks the records instead of the samples
-    constexpr bool XW_IN = MODE == FIELD_RADIANCE || MODE == FIELD_RADIANCE_TRUNK;       // x', w come from xw through src
-    static_assert(!(SAVE && (TRUNK || BRANCH)), "the sparse branches are an inference path");
+    constexpr bool FUSED = MODE == FIELD_ALL_FUSED || MODE == FIELD_RADIANCE_FUSED;      // trunk, ring append and branch pass in one launch
+    constexpr bool XW_IN = MODE == FIELD_RADIANCE || MODE == FIELD_RADIANCE_TRUNK || MODE == FIELD_RADIANCE_FUSED;       // x', w come from xw through src
+    static_assert(!(SAVE && (TRUNK || BRANCH || FUSED)), "the sparse branches are an inference path");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Ctx cx;
     cx.stream = packed + PACK_STREAM_OFF + (long)level * STREAM_FLOATS;
@@ -212,7 +236,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
     constexpr const Layer *Ly = kProg.layer;
     constexpr int L_START = BRANCH ? L_D0B : (XW_IN ? L_T0 : L_FIRST);      // first layer of this launch's walk through the stream
     cx.wrap_to = (uint32_t)Ly[L_START].stream_off;
-    cx.wrap_at = (MODE == FIELD_DEFORM) ? (uint32_t)Ly[L_T0].stream_off : (TRUNK ? (uint32_t)Ly[L_D0B].stream_off : (uint32_t)STREAM_FLOATS);
+    cx.wrap_at = (MODE == FIELD_DEFORM) ? (uint32_t)Ly[L_T0].stream_off : ((TRUNK || FUSED) ? (uint32_t)Ly[L_D0B].stream_off : (uint32_t)STREAM_FLOATS);      // (FUSED: chosen per tile)
     cx.off = cx.wrap_to;
     const float *grid = packed + PACK_GRID_OFF;
 
@@ -233,17 +257,57 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
     // FIELD_RADIANCE_TRUNK: the x', w row of the workgroup's NEXT tile is fetched while this one multiplies (its src entry at the start of
     // the tile, the dependent xw row behind T2), so a tile no longer starts with two dependent trips to HBM while the matrix pipe idles.
     // The addresses use the same P - 1 clamp; a workgroup with no next tile issues nothing.
-    constexpr bool XW_AHEAD = MODE == FIELD_RADIANCE_TRUNK && !DIAG_NOLOADS_TRUNK;
+    constexpr bool XW_AHEAD = (MODE == FIELD_RADIANCE_TRUNK && !DIAG_NOLOADS_TRUNK) || MODE == FIELD_RADIANCE_FUSED;
     f32x4 nx_a = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     float nx_w1 = 0.0f;
     int nx_src = 0;
-    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    // (FUSED) the workgroup's ring: uniform values, the same in every wave (they come from kernel arguments and from LDS words read behind a
+    // workgroup barrier), so every barrier below sits under workgroup-uniform control flow
+    uint32_t r_cnt = 0u, r_head = 0u, r_total = 0u, r_cap = 0u, r_base = 0u;
+    uint32_t r_it = 0u, r_tiles = 0u;      // iterations so far, this workgroup's tiles (32-bit: a 64-bit signed compare is a vector instruction, and what hangs on it leaves the scalar registers)
+    if constexpr (FUSED) {
+        r_tiles = (uint32_t)__builtin_amdgcn_readfirstlane((int)(ntiles / gridDim.x + ((long)blockIdx.x < ntiles % gridDim.x ? 1 : 0)));
+        r_cap = (uint32_t)sparse_ring_slots(r_tiles);
+        r_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)sparse_ring_base(ntiles, gridDim.x, blockIdx.x));
+    }
+    // (FUSED) which tile an iteration takes.  A workgroup's time depends on how many of ITS samples are live, and neighbouring rays are
+    // alike: with the fixed stride workgroup g would take the same image columns in every row of tiles.  So in the k-th full row of
+    // gridDim.x tiles workgroup g takes tile (g + 61 k) mod gridDim.x of that row -- a rotation, so every tile is still taken exactly once
+    // and the tiles running at one time are neighbours in memory as before -- and the leftover row keeps the fixed stride (workgroup g has
+    // a tile there iff g < ntiles % gridDim.x: what r_tiles and r_base count on).
+    const uint32_t r_rows = FUSED ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(ntiles / gridDim.x)) : 0u;
+    auto fused_tile = [&](uint32_t k) -> long {
+        const uint32_t col = k < r_rows ? (blockIdx.x + 61u * k) % gridDim.x : blockIdx.x;
+        return (long)k * gridDim.x + col;
+    };
+    for (long tile_it = blockIdx.x; FUSED || tile_it < ntiles; tile_it += gridDim.x, ++r_it) {
+        const long tile = FUSED ? fused_tile(r_it) : tile_it;
+        // (FUSED) has_tile: the iteration runs a trunk tile; do_branch: it ends in a branch pass over the ring's oldest records.  Past the
+        // last tile the iterations are branch passes only, until the ring is empty.
+        bool has_tile = true, do_branch = false;
+        uint32_t b_valid = 0u;      // records of this iteration's branch pass
+        if constexpr (FUSED) {
+            has_tile = r_it < r_tiles;
+            do_branch = has_tile ? r_cnt >= (uint32_t)F32_PTS_PER_WG : r_cnt > 0u;
+            if (!has_tile && !do_branch) break;
+            b_valid = r_cnt < (uint32_t)F32_PTS_PER_WG ? r_cnt : (uint32_t)F32_PTS_PER_WG;
+            if (has_tile) {      // known before L_ALPHA prefetches what follows it: on through the branches, or back to the first layer
+                cx.wrap_at = do_branch ? (uint32_t)STREAM_FLOATS : (uint32_t)Ly[L_D0B].stream_off;
+            } else {             // drain: the chunk in LDS is the first layer's; start the stream again at L_D0B (once per drain pass, at most 4 per launch)
+                cx.off = (uint32_t)Ly[L_D0B].stream_off;
+                cx.wrap_at = (uint32_t)STREAM_FLOATS;
+                cx.begin_chunk(CHF(L_D0B));
+#pragma unroll
+                for (int pc = 0; pc < (CHF(L_D0B) + PIECE_FLOATS - 1) / PIECE_FLOATS; ++pc) cx.issue_piece(pc);
+                cx.end_chunk();
+            }
+        }
         cx.refresh();
         // (a trunk launch of the 4-layer-trunk models has no rolled layer loop, so the stream offset of every chunk is the same constant
         // in every tile and LICM precomputes all ~100 LDS-DMA source addresses outside the persistent loop -- a kilobyte of scratch per
         // lane -- unless the offset is opaque per tile; likewise the encodings' per-lane octave selectors and the lane quarter)
         int q_tile = cx.q;
-        if constexpr (TRUNK) { asm volatile("" : "+s"(cx.off)); asm volatile("" : "+v"(q_tile)); }
+        if constexpr (TRUNK || FUSED) { asm volatile("" : "+s"(cx.off)); asm volatile("" : "+v"(q_tile)); }
         const int q = q_tile;
         const long p_raw = tile * F32_PTS_PER_WG + cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15);
         const long p = p_raw < P ? p_raw : P - 1;
@@ -278,13 +342,15 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             smp = __float_as_int(a[3]);
             if (q == 0) { stash[0] = a[0]; stash[1] = a[1]; stash[2] = a[2]; }
         } else if constexpr (!XW_IN) {
+            if (!FUSED || has_tile) {
             const float *rp = rays + (p / S) * ray_stride;
             const float z = zvals[p];
 #pragma unroll
             for (int i = 0; i < 3; ++i) x[i] = rp[i] + rp[3 + i] * z;          // train_utils.py:115
+            }
         } else if constexpr (XW_AHEAD) {
-            if (q == 0) {
-                if (tile == (long)blockIdx.x) {      // the workgroup's first tile: nothing was fetched ahead
+            if (q == 0 && (!FUSED || has_tile)) {
+                if (FUSED ? r_it == 0u : tile == (long)blockIdx.x) {      // the workgroup's first tile: nothing was fetched ahead
                     const float *row = xw + ((p / S) * (long)xw_row + src[p]) * 8;
                     nx_a = *reinterpret_cast<const f32x4 *>(row);
                     nx_w1 = row[4];
@@ -298,13 +364,27 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             if (sv_on) { float *d = SVP(act::XW, 16); d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; }   // the grid backward reads x'
         }
         // (XW_AHEAD) this lane's sample of the workgroup's next tile
-        const bool has_next = XW_AHEAD && tile + gridDim.x < ntiles;
-        const long pn_raw = p_raw + (long)gridDim.x * F32_PTS_PER_WG;
+        const bool has_next = XW_AHEAD && (FUSED ? r_it + 1u < r_tiles : tile + gridDim.x < ntiles);
+        const long pn_raw = FUSED ? fused_tile(r_it + 1u) * F32_PTS_PER_WG + cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15) : p_raw + (long)gridDim.x * F32_PTS_PER_WG;
         const long p_next = pn_raw < P ? pn_raw : P - 1;
         if constexpr (XW_AHEAD) {
             if (has_next && q == 0) nx_src = src[p_next];
         }
+        // (FUSED) the header of this lane's record of the branch pass, fetched most of a trunk ahead: its sample index is what the raw row and
+        // the ray direction are addressed with.  Lanes past the count take the last record (and store nothing).  The youngest of the 128
+        // records may be of the previous tile, stored by another wave, so the load sits behind the first chunk barrier of this iteration: a
+        // drain pass has had the one of its stream restart, a tile issues it behind T0.
+        f32x4 b_hdr = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t b_slot = 0u;
+        if constexpr (FUSED) {
+            if (do_branch) {
+                const uint32_t j = (uint32_t)(cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15));
+                b_slot = r_base + r_head + (j < b_valid ? j : b_valid - 1u);      // (r_head is a multiple of 128, as r_cap is: a pass never straddles the ring's end)
+                if (!has_tile) b_hdr = sp.hdr[b_slot];
+            }
+        }
         if constexpr (!XW_IN && !BRANCH) {
+        if (!FUSED || has_tile) {
 #if SAHS_MODEL == 2
         // no deformation nets (use_warp False, use_ambient False): the template is queried at the raw point (models.py:316-327)
         if (q == 0) {
@@ -384,6 +464,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             *reinterpret_cast<f32x4 *>(row) = f32x4{stash[0], stash[1], stash[2], stash[3]};
             row[4] = stash[4];
         }
+        }
         }   // !XW_IN && !BRANCH
         if constexpr (MODE == FIELD_DEFORM) continue;      // the stream has wrapped to the warp field's first layer
         __builtin_amdgcn_wave_barrier();
@@ -401,15 +482,15 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             const f32x4 *rec = sp.feat + (p >> 4) * (16 * 64) + q * 16 + (p & 15);
 #pragma unroll
             for (int b = 0; b < 16; ++b) feat[b] = rec[b * 64];
-        } else {
+        } else if (!FUSED || has_tile) {
             f32x4 h[16];
-            if constexpr (TRUNK) {
+            if constexpr (TRUNK || FUSED) {
                 // PE(x'), PE(w) feed T0 and, re-injected, the skip layer T3A.  The TRUNK instances stop behind fc_alpha, hold no ray direction
                 // or grid blocks and compile to about 200 VGPRs, so the 24 registers can stay live through T1, T2 and the encodings be built
                 // once per tile (a build is ~1,000 VALU instructions per wave, and all eight waves run it at the same moment, the matrix pipe
                 // idle).  Measured per launch (W512 frame, LAB_NOTES.md): -1.3 % for the fine trunk; for FIELD_ALL_TRUNK, whose tile also runs
                 // the deformation nets, the -0.8 % is below that launch's own spread, and it keeps the rebuild like the dense instances.
-                constexpr bool ENC_ONCE = MODE == FIELD_RADIANCE_TRUNK && !DIAG_ENC2;
+                constexpr bool ENC_ONCE = (MODE == FIELD_RADIANCE_TRUNK && !DIAG_ENC2) || MODE == FIELD_RADIANCE_FUSED;
                 f32x4 in_tr[KB_XYZ + KB_AMB];
                 auto build_enc = [&]() {
                     const float xw[3] = {stash[0], stash[1], stash[2]}, amb[2] = {stash[3], stash[4]};
@@ -427,6 +508,9 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
                 };
                 build_enc();
                 dense<KB_XYZ, KB_AMB, 16, CHF(L_T1)>(cx, in_tr, in_tr + KB_XYZ, h, Ly[L_T0].bias_off, false, 0.01f);
+                if constexpr (FUSED) {
+                    if (do_branch) b_hdr = sp.hdr[b_slot];
+                }
                 dense<16, 0, 16, CHF(L_T2)>(cx, h, nullptr, feat, Ly[L_T1].bias_off, false, 0.01f);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) h[i] = feat[i];
@@ -501,7 +585,63 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             dense_sv<SAVE, 16, 0, 16, CHF(L_ALPHA)>(cx, h, nullptr, feat, Ly[L_FEAT].bias_off, false, 1.0f, SV(act::FEAT, 256));
             if (dump) dsl[13] = feat[0][0];
         }
-        if constexpr (!BRANCH) dense<16, 0, 1, (TRUNK ? CHF(L_START) : CHF(L_D0B))>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+        if constexpr (FUSED) {      // (a uniform two-way copy of this one-tile layer: NEXT is a compile-time size)
+            if (has_tile) {
+                if (do_branch) dense<16, 0, 1, CHF(L_D0B)>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+                else dense<16, 0, 1, CHF(L_START)>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+            }
+        } else if constexpr (!BRANCH) dense<16, 0, 1, (TRUNK ? CHF(L_START) : CHF(L_D0B))>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+        if constexpr (FUSED) {
+            if (has_tile) {
+                if (p_raw < P) *reinterpret_cast<f32x4 *>(raw + p * D_RAW + 4 * q) = fin[0];
+                // live: the same expression as the trunk instances' below
+                const long ray = p / S;
+                const bool last = (p - ray * S) == S - 1;
+                const float sg = fin[0][3] + (sp.noise != nullptr ? sp.noise[p] : 0.0f);
+                const bool live = q == 3 && p_raw < P && (last ? sp.has_bg == 0 : sg > 0.0f);
+                const uint32_t mask = (uint32_t)(__ballot(live) >> 48);
+                // slots: the waves' live counts through LDS (read again only after the many chunk barriers of the next tile)
+                uint32_t *cnts = reinterpret_cast<uint32_t *>(lds + LDS_TOTAL_FLOATS);
+                if (cx.lane == 0) cnts[cx.wave] = (uint32_t)__popc(mask);
+                __syncthreads();
+                uint32_t before = 0u, all = 0u;
+#pragma unroll
+                for (int w = 0; w < F32_THREADS / WAVE; ++w) {
+                    const uint32_t c = cnts[w];
+                    all += c;
+                    before += w < cx.wave ? c : 0u;
+                }
+                before = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
+                all = (uint32_t)__builtin_amdgcn_readfirstlane((int)all);
+                uint32_t tail = r_head + r_cnt;
+                if (tail >= r_cap) tail -= r_cap;
+                const int j = cx.lane & 15;
+                if ((mask >> j) & 1u) {
+                    uint32_t idx = tail + before + (uint32_t)__popc(mask & ((1u << j) - 1u));
+                    if (idx >= r_cap) idx -= r_cap;
+                    const uint32_t slot = r_base + idx;
+                    f32x4 *rec = sp.feat + (long)(slot >> 4) * (16 * 64) + q * 16 + (slot & 15u);
+#pragma unroll
+                    for (int b = 0; b < 16; ++b) rec[b * 64] = feat[b];
+                    if (q == 0) sp.hdr[slot] = f32x4{stash[0], stash[1], stash[2], __int_as_float((int)p)};
+                }
+                r_cnt += all;
+                r_total += all;
+            }
+            if (!do_branch) continue;      // the stream has wrapped to the first layer
+            // the branch pass: x' -> stash, the FINAL tile behind fc_alpha from the raw row, feat from the record (as FIELD_BRANCH)
+            smp = __float_as_int(b_hdr[3]);
+            __builtin_amdgcn_wave_barrier();
+            if (q == 0) { stash[0] = b_hdr[0]; stash[1] = b_hdr[1]; stash[2] = b_hdr[2]; }
+            __builtin_amdgcn_wave_barrier();
+            fin[0] = *reinterpret_cast<const f32x4 *>(raw + smp * D_RAW + 4 * q);
+            const f32x4 *rec = sp.feat + (long)(b_slot >> 4) * (16 * 64) + q * 16 + (b_slot & 15u);
+#pragma unroll
+            for (int b = 0; b < 16; ++b) feat[b] = rec[b * 64];
+            r_cnt -= b_valid;
+            r_head += (uint32_t)F32_PTS_PER_WG;
+            if (r_head >= r_cap) r_head -= r_cap;
+        }
         if constexpr (TRUNK) {
             if (p_raw < P) *reinterpret_cast<f32x4 *>(raw + p * D_RAW + 4 * q) = fin[0];
             // live: the composite will give the sample a weight that can be non-zero (render_ops.hip: sg = max(sigma + noise, 0), the same
@@ -585,7 +725,14 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             if (dump) dsl[17] = sn[0][0];
             dense<8, 0, 1, CHF(L_START)>(cx, sn, nullptr, fin, 0, true, 1.0f);
         }
-        if (p_raw < P) *reinterpret_cast<f32x4 *>(raw + smp * D_RAW + 4 * q) = fin[0];   // cat((rgb, seg, alpha)) modules.py:295
+        if (FUSED ? (uint32_t)(cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15)) < b_valid : p_raw < P)
+            *reinterpret_cast<f32x4 *>(raw + smp * D_RAW + 4 * q) = fin[0];   // cat((rgb, seg, alpha)) modules.py:295
+    }
+    if constexpr (FUSED) {      // the pass's live count, once per workgroup (no value returned); the second head word says which path ran
+        if (threadIdx.x == 0) {
+            if (r_total != 0u) atomicAdd(sp.count, r_total);
+            if (blockIdx.x == 0) sp.count[1] = 1u;
+        }
     }
 }
 
@@ -601,7 +748,7 @@ static int launch_field(const float *packed, const float *frame, int level, long
 {
     const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG;
     const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    const size_t lds_bytes = (size_t)LDS_TOTAL_FLOATS * sizeof(float);
+    const size_t lds_bytes = (size_t)(LDS_TOTAL_FLOATS + ((MODE == FIELD_ALL_FUSED || MODE == FIELD_RADIANCE_FUSED) ? LDS_RING_FLOATS : 0)) * sizeof(float);
     static sahs_once::Flags attr_set;       // the large-LDS attribute is per device (and per instantiation)
     hipError_t ae = sahs_once::per_device(attr_set, [&]() {
         return hipFuncSetAttribute(reinterpret_cast<const void *>(field_forward_f32_kernel<SAVE, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -672,14 +819,25 @@ extern "C" int SAHS_SYM(sahs_field_forward_f32_split_bits_launch)(const float *p
 // ws: sahs_field_f32_sparse_ws_bytes(cap) bytes, 16-byte aligned: [record count, zeroed by the caller before the trunk launch | headers |
 // feat groups]; cap: record slots, a multiple of 128 and at least P (every sample may be live).  noise / has_bg: the composite's noise of
 // these samples (or null) and whether it is given a background prior -- what decides which samples are live.
+// The fused instances (see the kernel's MODE): stage 3 = FIELD_ALL_FUSED, stage 4 = FIELD_RADIANCE_FUSED, one launch for the whole pass; the
+// workspace then holds the workgroups' rings, sahs_field_f32_sparse_ring_slots(P, num_cu) slots (never more than P rounded up to 128), and
+// cap only has to cover those.  The launch adds the pass's live count to the head's first word and sets its second word to 1.
 extern "C" long SAHS_SYM(sahs_field_f32_sparse_ws_bytes)(long cap) { return SPARSE_HEAD_BYTES + cap * SPARSE_RECORD_BYTES; }
+extern "C" long SAHS_SYM(sahs_field_f32_sparse_ring_slots)(long P, int num_cu)
+{
+    if (P <= 0 || num_cu < 1) return 0;
+    const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG, grid = ntiles < num_cu ? ntiles : num_cu;
+    return sparse_ring_base(ntiles, grid, grid);
+}
 extern "C" int SAHS_SYM(sahs_field_forward_f32_sparse_launch)(const float *packed, const float *frame, int level, int stage, long P, int S,
                                                     const float *rays, int ray_stride, const float *zvals, float *raw, float *xw, int xw_row,
                                                     int xw_col0, const int *src, const float *noise, int has_bg, void *ws, long cap, int num_cu,
                                                     hipStream_t stream)
 {
     if (P <= 0) return 0;
-    if (ws == nullptr || cap < P || cap % F32_PTS_PER_WG != 0 || cap > (1L << 30)) return -4;
+    const bool fused = stage == 3 || stage == 4;
+    if (ws == nullptr || cap % F32_PTS_PER_WG != 0 || cap > (1L << 30)) return -4;
+    if (cap < (fused ? SAHS_SYM(sahs_field_f32_sparse_ring_slots)(P, num_cu) : P)) return -4;
     char *base = static_cast<char *>(ws);
     SparseArgs sp{noise, reinterpret_cast<unsigned int *>(base), reinterpret_cast<f32x4 *>(base + SPARSE_HEAD_BYTES),
                   reinterpret_cast<f32x4 *>(base + SPARSE_HEAD_BYTES + cap * 16), (unsigned int)cap, has_bg};
@@ -687,9 +845,13 @@ extern "C" int SAHS_SYM(sahs_field_forward_f32_sparse_launch)(const float *packe
         return launch_field<false, FIELD_ALL_TRUNK>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream, nullptr, sp);
     if (stage == 2)      // (P: an upper bound of the record count, for the grid)
         return launch_field<false, FIELD_BRANCH>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, nullptr, 0, 0, nullptr, num_cu, stream, nullptr, sp);
+    if (stage == 3)
+        return launch_field<false, FIELD_ALL_FUSED>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream, nullptr, sp);
 #if SAHS_MODEL != 2
     if (stage == 1)
         return launch_field<false, FIELD_RADIANCE_TRUNK>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, xw, xw_row, 0, src, num_cu, stream, nullptr, sp);
+    if (stage == 4)
+        return launch_field<false, FIELD_RADIANCE_FUSED>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, xw, xw_row, 0, src, num_cu, stream, nullptr, sp);
 #endif
     return -2;
 }

@@ -68,6 +68,7 @@ int sahs_conditioning_backward_launch(const float *flat, const float *audio, con
                                                       int xw_row, int xw_col0, const int *src, float *actbuf, uint32_t *bits,           \
                                                       int num_cu, hipStream_t stream);                                                  \
     long sahs_field_f32_sparse_ws_bytes##sfx(long cap);                                                                                 \
+    long sahs_field_f32_sparse_ring_slots##sfx(long P, int num_cu);                                                                     \
     int sahs_field_forward_f32_sparse_launch##sfx(const float *packed, const float *frame, int level, int stage, long P, int S,        \
                                                   const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,         \
                                                   int xw_row, int xw_col0, const int *src, const float *noise, int has_bg, void *ws,    \
