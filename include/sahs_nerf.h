@@ -317,21 +317,19 @@ int sahs_model_render_rays_rows(int model, const void *packed, const float *fram
 /* sahs_model_render_rays_rows with SPARSE BRANCHES (fp32; any other precision is handed to sahs_model_render_rays_rows unchanged).  The
  * composite gives a sample whose sigma + noise is <= 0 the weight exactly 0, and with a background prior it replaces the last sample's
  * channels, so the colour and seg branches of such samples are never used.  Every radiance evaluation of the chain (both the plain chain and,
- * with xw / src / z_new, the shared-deformation one) runs as a trunk launch up to fc_alpha, which appends feat, x' and the index of every LIVE
- * sample to the record workspace, and a branch launch over those records only; rows, z_c, z_f and weights are bit-identical to
+ * with xw / src / z_new, the shared-deformation one) is ONE launch per pass: every persistent workgroup runs its samples up to fc_alpha,
+ * appends feat, x' and the index of every LIVE sample to a private ring of records in the workspace, and runs the branch layers itself
+ * over the oldest records whenever the ring holds a tile's worth (128), then drains it.  rows, z_c, z_f and weights are bit-identical to
  * sahs_model_render_rays_rows.
  * raw: the row of a live sample is bit-identical too; of a zero-weight sample only column 15 (sigma) is a network output -- columns 0..14
  * hold the fc_rgb / fc_seg biases (the FINAL tile as fc_alpha leaves it), finite and the same in both chains, NOT the sample's logits.
- * ws, ws_bytes: the record workspace, 16-byte aligned; sahs_model_render_sparse_workspace_bytes(model, samples) is the size that takes
- * `samples` sample evaluations in one slab.  A pass of N * S samples is cut into equal ray slabs whose samples all fit (every sample may
- * be live), so any size of at least one 128-record tile and one ray's samples works; smaller ones are refused (code 5).  No host
- * synchronisation: the branch launch reads the record count from device memory.  The launch probe sees ONE record per pass, of the dense
- * launch's kind and sample count.
- * A workspace that holds the record rings of the one-launch form -- sahs_model_render_sparse_fused_workspace_bytes(model, samples) bytes
- * on the current device: at most 512 slots per compute unit, never more than sahs_model_render_sparse_workspace_bytes(model, samples) --
- * takes each pass in ONE launch instead: every persistent workgroup appends its live samples to a private ring and runs the branch layers
- * itself whenever the ring holds a tile's worth.  Same results, bit for bit.  The first two 32-bit words of the workspace afterwards hold
- * the live records of the last launch that appended (fused: the whole pass; slabs: the last slab) and 1 / 0 for fused / slabs. */
+ * ws, ws_bytes: the record workspace, 16-byte aligned.  It has to hold the rings of the larger pass, N * (Sc + nf) samples:
+ * sahs_model_render_sparse_fused_workspace_bytes(model, samples) is the exact need on the current device (at most 512 record slots per
+ * compute unit, 0.13 GiB on 256 of them), sahs_model_render_sparse_workspace_bytes(model, samples) an upper bound that does not depend on
+ * the device (every sample a slot, rounded up to a tile).  A workspace that holds less, or a pass of more than 2^30 samples (a record
+ * holds its sample's index as an int), is refused with code 5 before anything is launched.  No host synchronisation.  The launch probe sees
+ * ONE record per pass, of the dense launch's kind and sample count.  The first two 32-bit words of the workspace afterwards hold the live
+ * records of the last pass and 1 (once a sparse pass ran). */
 size_t sahs_model_render_sparse_workspace_bytes(int model, long samples);
 size_t sahs_model_render_sparse_fused_workspace_bytes(int model, long samples);
 int sahs_model_render_rays_rows_sparse(int model, const void *packed, const float *frame, int precision, long N, const float *rays,

@@ -306,10 +306,10 @@ struct ModelFns {
     decltype(&sahs_field_forward_f32_launch) f32;
     decltype(&sahs_field_forward_f32_split_launch) f32_split;
     decltype(&sahs_field_forward_f32_split_bits_launch) f32_split_bits;
-    // ... and the inference render's sparse branches: trunk launch + compacted branch launch, and the bytes of their record workspace
+    // ... and the inference render's sparse branches: the one-launch pass, the bytes of a record workspace and the slots a pass's rings need
     decltype(&sahs_field_forward_f32_sparse_launch) f32_sparse;
     decltype(&sahs_field_f32_sparse_ws_bytes) f32_sparse_ws_bytes;
-    decltype(&sahs_field_f32_sparse_ring_slots) f32_sparse_ring_slots;      // slots the one-launch (fused) form of a pass needs
+    decltype(&sahs_field_f32_sparse_ring_slots) f32_sparse_ring_slots;
     // backward (field_bwd.hip): per-layer walk, cut at the (x', w) seam, fused walk
     long (*bwd_ws_words)(long);
     decltype(&sahs_field_backward_launch) bwd;
@@ -835,12 +835,11 @@ int sahs_model_render_rays_rows(int model, const void *packed, const float *fram
                              stream, row_ld, row_ld);
 }
 
-// ---- sparse branches (fp32 inference render): see csrc/field_f32.hip, FIELD_*_FUSED / FIELD_*_TRUNK / FIELD_BRANCH ----
-// One radiance evaluation of the render chain.  A workspace that holds the workgroups' record rings (never more than the pass's samples
-// rounded up to a tile, at most 512 slots per CU) takes the pass in ONE fused launch; a smaller one takes it as trunk + branch launches
-// over ray slabs sized to the record workspace.  Either way ONE probe record of the kind and sample count the dense launch has, and the
-// workspace's head afterwards holds [live records of the last launch that appended | 1 if that pass ran fused, 0 if it ran slabs].
-// stage: 0 whole network up to fc_alpha (coarse pass, plain chain's fine pass), 1 radiance trunk on x', w from xw through src.
+// ---- sparse branches (fp32 inference render): see csrc/field_f32.hip, FIELD_ALL_FUSED / FIELD_RADIANCE_FUSED ----
+// One radiance evaluation of the render chain: ONE launch over the pass, the workspace holding the workgroups' record rings (never more
+// than the pass's samples rounded up to a tile, at most 512 slots per CU; the caller has checked that they fit), and ONE probe record of
+// the kind and sample count the dense launch has.  The workspace's head afterwards holds [live records of the pass | 1].
+// stage: 0 whole network (coarse pass, plain chain's fine pass), 1 radiance nets on x', w from xw through src.
 static long sparse_capacity(int model, size_t ws_bytes)      // record slots (a multiple of 128) a workspace of ws_bytes holds
 {
     const ModelFns &m = kModels[model];
@@ -854,37 +853,13 @@ static int field_forward_sparse(const char *who, int model, const float *pk, con
                                 const float *noise, int has_bg, void *ws, long cap, hipStream_t st)
 {
     const ModelFns &m = kModels[model];
-    // (a record's header holds its sample index as an int: a pass of more than 2^30 samples goes through slabs, which are at most that long)
-    if (N * S <= (1L << 30) && cap >= m.f32_sparse_ring_slots(N * S, num_cus())) {
-        int e = probed(probe_kind(model, SAHS_F32, level, part), N * S, st, [&] {
-            hipError_t he = hipMemsetAsync(ws, 0, 8, st);
-            if (he != hipSuccess) return (int)he;
-            return m.f32_sparse(pk, frame, level, stage + 3, N * S, S, rays, ray_stride, z, raw, xw, xw_row, 0, src, noise, has_bg, ws, cap, num_cus(), st);
-        });
-        if (e == -4) return fail(5, "%s: the sparse-branch launcher refused its record workspace (%ld slots for the rings of %ld samples)", who, cap, N * S);
-        if (e < 0) return fail(4, "%s: the sparse-branch launcher has no stage %d for this model", who, stage + 3);
-        return e ? hip_fail(who, e) : 0;
-    }
-    const long per = cap / S;      // rays per slab in the worst case: every sample live
-    if (per < 1) return fail(5, "%s: the sparse-branch workspace holds %ld records, one ray has %d samples", who, cap, S);
-    const long nslab = (N + per - 1) / per, step = (N + nslab - 1) / nslab;      // equal slabs
     int e = probed(probe_kind(model, SAHS_F32, level, part), N * S, st, [&] {
-        for (long r0 = 0; r0 < N; r0 += step) {
-            const long n = N - r0 < step ? N - r0 : step, s0 = r0 * S;
-            hipError_t he = hipMemsetAsync(ws, 0, 8, st);
-            if (he != hipSuccess) return (int)he;
-            int le = m.f32_sparse(pk, frame, level, stage, n * S, S, rays + r0 * ray_stride, ray_stride, z ? z + s0 : nullptr, raw + s0 * 16,
-                                  xw ? xw + r0 * xw_row * 8 : nullptr, xw_row, 0, src ? src + s0 : nullptr, noise ? noise + s0 : nullptr, has_bg, ws,
-                                  cap, num_cus(), st);
-            if (le) return le;
-            le = m.f32_sparse(pk, frame, level, 2, n * S, S, rays + r0 * ray_stride, ray_stride, nullptr, raw + s0 * 16, nullptr, 0, 0, nullptr, nullptr,
-                              has_bg, ws, cap, num_cus(), st);
-            if (le) return le;
-        }
-        return 0;
+        hipError_t he = hipMemsetAsync(ws, 0, 8, st);
+        if (he != hipSuccess) return (int)he;
+        return m.f32_sparse(pk, frame, level, stage, N * S, S, rays, ray_stride, z, raw, xw, xw_row, 0, src, noise, has_bg, ws, cap, num_cus(), st);
     });
-    // (negative: the launcher's own refusals, not HIP errors -- unreachable through the checks above, named in case a caller's change breaks them)
-    if (e == -4) return fail(5, "%s: the sparse-branch launcher refused its record workspace (%ld slots for slabs of %ld samples)", who, cap, step * S);
+    // (negative: the launcher's own refusals, not HIP errors -- unreachable through the caller's checks, named in case a change breaks them)
+    if (e == -4) return fail(5, "%s: the sparse-branch launcher refused its record workspace (%ld slots for the rings of %ld samples)", who, cap, N * S);
     if (e < 0) return fail(4, "%s: the sparse-branch launcher has no stage %d for this model", who, stage);
     return e ? hip_fail(who, e) : 0;
 }
@@ -917,10 +892,17 @@ int sahs_model_render_rays_rows_sparse(int model, const void *packed, const floa
     REQUIRE(packed && frame && rays && z_c && raw && weights && N >= 0 && Sc >= 1 && nf >= 0 && Sc + nf <= 256 && ray_stride >= 8, who);
     REQUIRE(nf == 0 || z_f, who);
     REQUIRE(ws && ALIGNED16(ws) && ALIGNED16(packed) && ALIGNED16(frame) && ALIGNED16(raw) && (!xw || ALIGNED16(xw)), who);
-    const long cap = sparse_capacity(model, ws_bytes);
-    if (cap < 128)
-        return fail(5, "%s: a sparse-branch workspace of %zu bytes holds less than one tile of 128 records (sahs_model_render_sparse_workspace_bytes)",
-                    who, ws_bytes);
+    // refused before the first launch: a pass the rings cannot take (one size serves both passes; the fine pass has the larger rings, or equal)
+    const long cap = sparse_capacity(model, ws_bytes), all = N * (long)(Sc + nf);
+    if (all > (1L << 30))
+        return fail(5, "%s: a pass of %ld samples is more than 2^30, and a record's header holds the sample index as an int: render fewer rays "
+                       "per call (sahs_model_render_sparse_fused_workspace_bytes sizes passes up to 2^30 samples, %ld record slots; %ld given)",
+                    who, all, kModels[model].f32_sparse_ring_slots(1L << 30, num_cus()), cap);
+    const long need_c = kModels[model].f32_sparse_ring_slots(N * Sc, num_cus()), need_f = kModels[model].f32_sparse_ring_slots(all, num_cus());
+    const long need = need_c > need_f ? need_c : need_f;
+    if (cap < need)
+        return fail(5, "%s: a sparse-branch workspace of %zu bytes holds %ld record slots, the rings of this render need %ld "
+                       "(sahs_model_render_sparse_fused_workspace_bytes)", who, ws_bytes, cap, need);
     const bool shared = xw && src && z_new && nf > 0 && kModels[model].deformation_nets;
     const float *pk = (const float *)packed;
     const int Sf = Sc + nf, has_bg = bg != nullptr;
@@ -936,7 +918,7 @@ int sahs_model_render_rays_rows_sparse(int model, const void *packed, const floa
                                       row_ld, row_ld, st);
     if (e) return hip_fail(who, e);
     if (nf == 0) return 0;
-    if (shared) {      // the deformation nets once per depth (sahs_model_render_rays_rows), the fine pass's radiance nets as trunk + branch
+    if (shared) {      // the deformation nets once per depth (sahs_model_render_rays_rows), the fine pass's radiance nets with sparse branches
         if ((e = sahs_resample_merge(N, Sc, nf, z_c, weights, u, z_new, z_f, src, stream))) return e;
         if ((e = sahs_model_field_forward_split(model, packed, frame, precision, 1, 1, N, nf, rays, ray_stride, z_new, nullptr, xw, Sf, Sc, nullptr, stream))) return e;
         if ((e = field_forward_sparse(who, model, pk, frame, 1, 1, 2, N, Sf, rays, ray_stride, nullptr, raw, xw, Sf, src, noise_f, has_bg, ws, cap, st))) return e;

@@ -122,6 +122,18 @@ __device__ __forceinline__ void grid_blocks(const float *__restrict__ grid, floa
     }
 }
 
+// the radiance trunk's input blocks [PE(x') | PE(w)] from a lane's stash {x'0 x'1 x'2 w0 w1}: they feed T0 and, re-injected, the skip layer T3A
+__device__ __forceinline__ void trunk_encodings(const float *stash, int q, f32x4 *enc)
+{
+    const float xw[3] = {stash[0], stash[1], stash[2]}, amb[2] = {stash[3], stash[4]};
+    pe_blocks<3, L_XYZ, KB_XYZ>(xw, q, enc);
+#if SAHS_MODEL != 2
+    pe_blocks<AMB_DIM, L_AMB, KB_AMB, AMB_INC>(amb, q, enc + KB_XYZ);
+#else
+    (void)amb;
+#endif
+}
+
 #define CHF(id) (kProg.layer[id].G * kProg.layer[id].KB * 256)   /* floats in one chunk of layer id */
 
 // SAVE: also store every layer's activations (sahs::act layout, 19 KB/sample) for field_bwd.hip
@@ -136,21 +148,22 @@ __device__ __forceinline__ void grid_blocks(const float *__restrict__ grid, floa
 //
 // The inference render also splits the radiance evaluation at fc_alpha (sparse branches).  The composite gives a sample whose sigma + noise
 // is <= 0 the weight exactly 0 (and replaces the last sample's channels by the background prior), so its colour and seg logits are never
-// used: a TRUNK launch runs the network up to L_ALPHA, stores the FINAL tile as it stands there (rows 0..14 the fc_rgb / fc_seg biases,
-// row 15 sigma) as the sample's raw row, and appends feat, x' and the sample index of every LIVE sample to a compact record buffer; a
-// FIELD_BRANCH launch then runs L_D0B..L_SEG over the records only and overwrites those samples' raw rows.  Columns of an MFMA tile are
-// independent, so a live sample's row has the bits of the one-launch evaluation whatever slot it lands in.
-//   FIELD_ALL_TRUNK = FIELD_ALL up to L_ALPHA, FIELD_RADIANCE_TRUNK = FIELD_RADIANCE up to L_ALPHA, FIELD_BRANCH = the two branches
-//
-// The fused sparse instances do both in ONE launch per pass.  Every persistent workgroup keeps a private FIFO ring of records in the
-// workspace: a tile runs the network up to L_ALPHA, appends its live samples to the ring (slots from per-wave live counts through LDS: no
-// global atomic), and -- when the ring held a tile's worth (128) at the START of the tile -- goes on through L_D0B..L_SEG over the 128
-// oldest records instead of wrapping at L_D0B.  All of those were stored during earlier tiles of the same workgroup (same CU, workgroup
-// barriers in between), so the loads are disjoint from this tile's stores.  After its last tile the workgroup drains the ring in
-// branch-only iterations (the last one partial: lanes past the count redo the last record and store nothing).
-//   FIELD_ALL_FUSED = FIELD_ALL_TRUNK + branches, FIELD_RADIANCE_FUSED = FIELD_RADIANCE_TRUNK + branches
-enum { FIELD_ALL = 0, FIELD_DEFORM = 1, FIELD_RADIANCE = 2, FIELD_ALL_TRUNK = 3, FIELD_RADIANCE_TRUNK = 4, FIELD_BRANCH = 5, FIELD_ALL_FUSED = 6,
-       FIELD_RADIANCE_FUSED = 7 };
+// used.  The dense modes (FIELD_ALL, FIELD_DEFORM, FIELD_RADIANCE) evaluate every layer of their part for every sample; the fused sparse
+// modes run the branches L_D0B..L_SEG for the LIVE samples only, in the same launch:
+//   FIELD_ALL_FUSED = FIELD_ALL with sparse branches, FIELD_RADIANCE_FUSED = FIELD_RADIANCE with sparse branches
+//  * the ring.  Every persistent workgroup keeps a private FIFO ring of records (feat, x' and the sample index of a live sample) in the
+//    workspace.  A tile runs the network up to L_ALPHA, stores the FINAL tile as it stands there (rows 0..14 the fc_rgb / fc_seg biases,
+//    row 15 sigma) as the samples' raw rows and appends its live samples to the ring (slots from per-wave live counts through LDS: no
+//    global atomic).  When the ring held a tile's worth (128) at the START of the tile, the iteration goes on through L_D0B..L_SEG over
+//    the 128 oldest records instead of wrapping at L_D0B, and overwrites those samples' raw rows.  All of those records were stored during
+//    earlier tiles of the same workgroup (same CU, workgroup barriers in between), so the loads are disjoint from this tile's stores.
+//    Columns of an MFMA tile are independent, so a live sample's row has the bits of the dense evaluation whatever slot it lands in.
+//  * the drain.  After its last tile the workgroup empties the ring in branch-only iterations (the last one partial: lanes past the count
+//    redo the last record and store nothing).
+//  * the tile rotation: which tile an iteration takes (fused_tile below), so that a workgroup's share of live samples evens out.
+// The mode numbers are part of the instances' mangled names (build.py: NO_SCRATCH, tools/compare_isa.py); 3..5 were the trunk-launch +
+// branch-launch form this one replaced (LAB_NOTES.md).
+enum { FIELD_ALL = 0, FIELD_DEFORM = 1, FIELD_RADIANCE = 2, FIELD_ALL_FUSED = 6, FIELD_RADIANCE_FUSED = 7 };
 // Ring slots per workgroup of the fused instances.  The branch decision is taken from the count carried INTO a tile (>= 128), so that count
 // is at most 255 when a tile starts, a tile adds at most 128, and 383 slots can never overflow; a workgroup of T tiles appends at most
 // 128 T records in all.  Workgroup g's ring starts at the sum of its predecessors' slots.
@@ -158,58 +171,27 @@ constexpr int SPARSE_RING = 512;
 static_assert(SPARSE_RING >= 255 + 128 && SPARSE_RING % 128 == 0, "a ring holds the carried count plus one tile");
 __host__ __device__ constexpr long sparse_ring_slots(long tiles) { return tiles * F32_PTS_PER_WG < SPARSE_RING ? tiles * F32_PTS_PER_WG : SPARSE_RING; }
 // slots in front of workgroup g's ring (g == grid: all of them) when `grid` workgroups share ntiles tiles (every workgroup one tile of each
-// full row of `grid` tiles, workgroups g < ntiles % grid one more)
+// full row of `grid` tiles, workgroups g < ntiles % grid one more).  With grid = min(ntiles, CUs) the total never goes down as ntiles goes up
+// (one more tile is 128 slots more, or one workgroup's step from slots(t) to slots(t + 1) >= slots(t)), so a workspace sized for the
+// larger pass of a render holds the rings of the smaller one
 __host__ __device__ constexpr long sparse_ring_base(long ntiles, long grid, long g)
 {
     const long tlo = ntiles / grid, rem = ntiles % grid;
     return g * sparse_ring_slots(tlo) + (g < rem ? g : rem) * (sparse_ring_slots(tlo + 1) - sparse_ring_slots(tlo));
 }
 constexpr int LDS_RING_FLOATS = 16;      // fused instances: the waves' live counts of a tile, behind the stash
-// Record buffer of the sparse branches.  Records are taken in groups of 16 slots (one wave of the branch launch); a group's feat is laid
-// out [k-block 16][lane 64][4] like a weight fragment, so the branch launch loads it with whole 1-KB wave transactions.
+// The record workspace of the fused instances (the kernel's argument block; the launcher fills it from one allocation).  Records sit in
+// groups of 16 slots (one wave of a branch pass); a group's feat is laid out [k-block 16][lane 64][4] like a weight fragment, so a branch
+// pass loads it with whole 1-KB wave transactions.
 struct SparseArgs {
-    const float *noise;      // trunk: the composite's noise of these samples (N, S), or null
-    unsigned int *count;     // trunk: records appended so far (zeroed by the caller); branch: records to process
+    const float *noise;      // the composite's noise of these samples (N, S), or null: part of what decides which samples are live
+    unsigned int *count;     // head words: [0] += the pass's live count (zeroed by the caller), [1] = 1 once a sparse pass ran
     f32x4 *hdr;              // [cap] {x'0, x'1, x'2, sample index (int bits)}
     f32x4 *feat;             // [cap / 16][16][64]
-    unsigned int cap;        // slots (a multiple of 128, at least the samples of the trunk launch)
+    unsigned int cap;        // slots (a multiple of 128, at least the rings of the launch: sparse_ring_base(ntiles, grid, grid))
     int has_bg;              // a background prior replaces the last sample's channels
 };
 constexpr long SPARSE_HEAD_BYTES = 256, SPARSE_RECORD_BYTES = 16 + 16 * 16 * 4;
-// Timing-only switches of the sparse instances (tools/ablate.py; results are WRONG by construction, the shipped library has none of them):
-// what a tile's encodings, its prologue loads and its record append cost beside the MFMA layers.
-#if defined(SAHS_DIAG) && defined(SAHS_F32_ENC2)
-constexpr bool DIAG_ENC2 = true;             // trunk: build the encodings again before the skip layer (as the dense instances do)
-#else
-constexpr bool DIAG_ENC2 = false;
-#endif
-#if defined(SAHS_DIAG) && defined(SAHS_F32_NOENC)
-constexpr bool DIAG_NOENC = true;            // sparse instances: no sin_octave at all (a block is its lane's coordinates)
-#else
-constexpr bool DIAG_NOENC = false;
-#endif
-#if defined(SAHS_DIAG) && defined(SAHS_F32_NOLOADS_TRUNK)
-constexpr bool DIAG_NOLOADS_TRUNK = true;    // trunk: x', w (or the point) made up from the sample index instead of loaded
-#else
-constexpr bool DIAG_NOLOADS_TRUNK = false;
-#endif
-#if defined(SAHS_DIAG) && defined(SAHS_F32_NOLOADS_BRANCH)
-constexpr bool DIAG_NOLOADS_BRANCH = true;   // branch: header, raw row, feat, ray direction and grid corners made up instead of loaded
-#else
-constexpr bool DIAG_NOLOADS_BRANCH = false;
-#endif
-#if defined(SAHS_DIAG) && defined(SAHS_F32_NOAPPEND)
-constexpr bool DIAG_NOAPPEND = true;         // trunk: no record append (the branch launches then find no records)
-#else
-constexpr bool DIAG_NOAPPEND = false;
-#endif
-// (diag) a cheap stand-in for pe_blocks: lane-dependent values the compiler cannot fold
-template <int NB>
-__device__ __forceinline__ void diag_blocks(const float *v, int q, f32x4 *out)
-{
-#pragma unroll
-    for (int b = 0; b < NB; ++b) out[b] = f32x4{v[0], v[1], v[0] * (float)(q + b), v[1] + (float)b};
-}
 template <bool SAVE, int MODE>
 __global__ void __launch_bounds__(F32_THREADS, 2)
 field_forward_f32_kernel(const float *__restrict__ packed, const float *__restrict__ frame, int level, long P, int S,
@@ -218,13 +200,11 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
                          float *__restrict__ xw, int xw_row, int xw_col0, const int *__restrict__ src, uint32_t *__restrict__ bits, SparseArgs sp)
 {
 #if SAHS_MODEL == 2
-    static_assert(MODE == FIELD_ALL || MODE == FIELD_ALL_TRUNK || MODE == FIELD_BRANCH || MODE == FIELD_ALL_FUSED, "this model has no deformation nets to split off");
+    static_assert(MODE == FIELD_ALL || MODE == FIELD_ALL_FUSED, "this model has no deformation nets to split off");
 #endif
-    constexpr bool TRUNK = MODE == FIELD_ALL_TRUNK || MODE == FIELD_RADIANCE_TRUNK;      // stops behind L_ALPHA and appends the live samples' records
-    constexpr bool BRANCH = MODE == FIELD_BRANCH;                                        // walks the records instead of the samples
-    constexpr bool FUSED = MODE == FIELD_ALL_FUSED || MODE == FIELD_RADIANCE_FUSED;      // trunk, ring append and branch pass in one launch
-    constexpr bool XW_IN = MODE == FIELD_RADIANCE || MODE == FIELD_RADIANCE_TRUNK || MODE == FIELD_RADIANCE_FUSED;       // x', w come from xw through src
-    static_assert(!(SAVE && (TRUNK || BRANCH || FUSED)), "the sparse branches are an inference path");
+    constexpr bool FUSED = MODE == FIELD_ALL_FUSED || MODE == FIELD_RADIANCE_FUSED;      // sparse branches: trunk, ring append and branch pass in one launch
+    constexpr bool XW_IN = MODE == FIELD_RADIANCE || MODE == FIELD_RADIANCE_FUSED;       // x', w come from xw through src
+    static_assert(!(SAVE && FUSED), "the sparse branches are an inference path");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Ctx cx;
     cx.stream = packed + PACK_STREAM_OFF + (long)level * STREAM_FLOATS;
@@ -234,9 +214,9 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
     cx.q = cx.lane >> 4;
     cx.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr const Layer *Ly = kProg.layer;
-    constexpr int L_START = BRANCH ? L_D0B : (XW_IN ? L_T0 : L_FIRST);      // first layer of this launch's walk through the stream
+    constexpr int L_START = XW_IN ? L_T0 : L_FIRST;      // first layer of this launch's walk through the stream
     cx.wrap_to = (uint32_t)Ly[L_START].stream_off;
-    cx.wrap_at = (MODE == FIELD_DEFORM) ? (uint32_t)Ly[L_T0].stream_off : ((TRUNK || FUSED) ? (uint32_t)Ly[L_D0B].stream_off : (uint32_t)STREAM_FLOATS);      // (FUSED: chosen per tile)
+    cx.wrap_at = (MODE == FIELD_DEFORM) ? (uint32_t)Ly[L_T0].stream_off : (FUSED ? (uint32_t)Ly[L_D0B].stream_off : (uint32_t)STREAM_FLOATS);      // (FUSED: chosen per tile)
     cx.off = cx.wrap_to;
     const float *grid = packed + PACK_GRID_OFF;
 
@@ -249,15 +229,11 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         cx.end_chunk();
     }
 
-    if constexpr (BRANCH) {      // the points of this launch are the records the trunk launch left (no host synchronisation in between)
-        const unsigned int n = *sp.count;
-        P = n < sp.cap ? n : sp.cap;
-    }
     const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG;
-    // FIELD_RADIANCE_TRUNK: the x', w row of the workgroup's NEXT tile is fetched while this one multiplies (its src entry at the start of
+    // FIELD_RADIANCE_FUSED: the x', w row of the workgroup's NEXT tile is fetched while this one multiplies (its src entry at the start of
     // the tile, the dependent xw row behind T2), so a tile no longer starts with two dependent trips to HBM while the matrix pipe idles.
     // The addresses use the same P - 1 clamp; a workgroup with no next tile issues nothing.
-    constexpr bool XW_AHEAD = (MODE == FIELD_RADIANCE_TRUNK && !DIAG_NOLOADS_TRUNK) || MODE == FIELD_RADIANCE_FUSED;
+    constexpr bool XW_AHEAD = MODE == FIELD_RADIANCE_FUSED;
     f32x4 nx_a = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     float nx_w1 = 0.0f;
     int nx_src = 0;
@@ -303,11 +279,11 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             }
         }
         cx.refresh();
-        // (a trunk launch of the 4-layer-trunk models has no rolled layer loop, so the stream offset of every chunk is the same constant
+        // (a tile of the 4-layer-trunk models that stops behind fc_alpha has no rolled layer loop, so the stream offset of every chunk is the same constant
         // in every tile and LICM precomputes all ~100 LDS-DMA source addresses outside the persistent loop -- a kilobyte of scratch per
         // lane -- unless the offset is opaque per tile; likewise the encodings' per-lane octave selectors and the lane quarter)
         int q_tile = cx.q;
-        if constexpr (TRUNK || FUSED) { asm volatile("" : "+s"(cx.off)); asm volatile("" : "+v"(q_tile)); }
+        if constexpr (FUSED) { asm volatile("" : "+s"(cx.off)); asm volatile("" : "+v"(q_tile)); }
         const int q = q_tile;
         const long p_raw = tile * F32_PTS_PER_WG + cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15);
         const long p = p_raw < P ? p_raw : P - 1;
@@ -333,15 +309,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
 #define SBR(b, w) (sb_on ? bits_r + (long)(b) * Psv + sb_lane * (uint32_t)((w) >= 128 ? (w) / 128 : 1) : nullptr)
         float x[3] = {0.0f, 0.0f, 0.0f};
         long smp = p;            // the sample of this lane's point: its ray is smp / S, its raw row smp
-        if constexpr ((TRUNK && DIAG_NOLOADS_TRUNK) || (BRANCH && DIAG_NOLOADS_BRANCH)) {
-            const float t = (float)(p & 1023) * (1.0f / 1024.0f);
-            x[0] = t - 0.5f; x[1] = 0.25f - t; x[2] = 0.8f - t;
-            if (q == 0 && (XW_IN || BRANCH)) { stash[0] = x[0]; stash[1] = x[1]; stash[2] = x[2]; stash[3] = t; stash[4] = -t; }
-        } else if constexpr (BRANCH) {  // a record: x' -> stash (w is not needed behind the trunk)
-            const f32x4 a = sp.hdr[p];
-            smp = __float_as_int(a[3]);
-            if (q == 0) { stash[0] = a[0]; stash[1] = a[1]; stash[2] = a[2]; }
-        } else if constexpr (!XW_IN) {
+        if constexpr (!XW_IN) {
             if (!FUSED || has_tile) {
             const float *rp = rays + (p / S) * ray_stride;
             const float z = zvals[p];
@@ -349,8 +317,8 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             for (int i = 0; i < 3; ++i) x[i] = rp[i] + rp[3 + i] * z;          // train_utils.py:115
             }
         } else if constexpr (XW_AHEAD) {
-            if (q == 0 && (!FUSED || has_tile)) {
-                if (FUSED ? r_it == 0u : tile == (long)blockIdx.x) {      // the workgroup's first tile: nothing was fetched ahead
+            if (q == 0 && has_tile) {
+                if (r_it == 0u) {      // the workgroup's first tile: nothing was fetched ahead
                     const float *row = xw + ((p / S) * (long)xw_row + src[p]) * 8;
                     nx_a = *reinterpret_cast<const f32x4 *>(row);
                     nx_w1 = row[4];
@@ -364,8 +332,8 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             if (sv_on) { float *d = SVP(act::XW, 16); d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; }   // the grid backward reads x'
         }
         // (XW_AHEAD) this lane's sample of the workgroup's next tile
-        const bool has_next = XW_AHEAD && (FUSED ? r_it + 1u < r_tiles : tile + gridDim.x < ntiles);
-        const long pn_raw = FUSED ? fused_tile(r_it + 1u) * F32_PTS_PER_WG + cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15) : p_raw + (long)gridDim.x * F32_PTS_PER_WG;
+        const bool has_next = XW_AHEAD && r_it + 1u < r_tiles;
+        const long pn_raw = fused_tile(r_it + 1u) * F32_PTS_PER_WG + cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15);
         const long p_next = pn_raw < P ? pn_raw : P - 1;
         if constexpr (XW_AHEAD) {
             if (has_next && q == 0) nx_src = src[p_next];
@@ -383,7 +351,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
                 if (!has_tile) b_hdr = sp.hdr[b_slot];
             }
         }
-        if constexpr (!XW_IN && !BRANCH) {
+        if constexpr (!XW_IN) {
         if (!FUSED || has_tile) {
 #if SAHS_MODEL == 2
         // no deformation nets (use_warp False, use_ambient False): the template is queried at the raw point (models.py:316-327)
@@ -394,8 +362,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
 #else
         f32x4 pe_x[KB_XYZ];
         {
-            if constexpr (TRUNK && DIAG_NOENC) diag_blocks<KB_XYZ>(x, q, pe_x);
-            else pe_blocks<3, L_XYZ, KB_XYZ>(x, q, pe_x);
+            pe_blocks<3, L_XYZ, KB_XYZ>(x, q, pe_x);
             if (sv_on) {
 #pragma unroll
                 for (int b = 0; b < KB_XYZ; ++b) *reinterpret_cast<f32x4 *>(SVP(act::E, 16 * KB_XYZ) + 16 * b) = pe_x[b];
@@ -465,7 +432,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             row[4] = stash[4];
         }
         }
-        }   // !XW_IN && !BRANCH
+        }   // !XW_IN
         if constexpr (MODE == FIELD_DEFORM) continue;      // the stream has wrapped to the warp field's first layer
         __builtin_amdgcn_wave_barrier();
         if (dump) { dsl[0] = stash[0] - x[0]; dsl[1] = stash[1] - x[1]; dsl[2] = stash[2] - x[2]; dsl[3] = stash[3]; dsl[4] = stash[4]; }
@@ -473,44 +440,20 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         // ---- radiance trunk (modules.py:254-275) ----
         f32x4 fin[1];      // FINAL tile: raw[4q..4q+3] of this lane's point
         f32x4 feat[16];
-        if constexpr (BRANCH && DIAG_NOLOADS_BRANCH) {
-            fin[0] = f32x4{x[0], x[1], x[2], x[0]};
-#pragma unroll
-            for (int b = 0; b < 16; ++b) feat[b] = f32x4{x[0] * (float)b, x[1], x[2] + (float)q, x[0]};
-        } else if constexpr (BRANCH) {      // what the trunk launch left: the FINAL tile behind fc_alpha in the raw row, feat in the record
-            fin[0] = *reinterpret_cast<const f32x4 *>(raw + smp * D_RAW + 4 * q);
-            const f32x4 *rec = sp.feat + (p >> 4) * (16 * 64) + q * 16 + (p & 15);
-#pragma unroll
-            for (int b = 0; b < 16; ++b) feat[b] = rec[b * 64];
-        } else if (!FUSED || has_tile) {
+        if (!FUSED || has_tile) {
             f32x4 h[16];
-            if constexpr (TRUNK || FUSED) {
-                // PE(x'), PE(w) feed T0 and, re-injected, the skip layer T3A.  The TRUNK instances stop behind fc_alpha, hold no ray direction
-                // or grid blocks and compile to about 200 VGPRs, so the 24 registers can stay live through T1, T2 and the encodings be built
-                // once per tile (a build is ~1,000 VALU instructions per wave, and all eight waves run it at the same moment, the matrix pipe
-                // idle).  Measured per launch (W512 frame, LAB_NOTES.md): -1.3 % for the fine trunk; for FIELD_ALL_TRUNK, whose tile also runs
-                // the deformation nets, the -0.8 % is below that launch's own spread, and it keeps the rebuild like the dense instances.
-                constexpr bool ENC_ONCE = (MODE == FIELD_RADIANCE_TRUNK && !DIAG_ENC2) || MODE == FIELD_RADIANCE_FUSED;
+            if constexpr (FUSED) {      // (T0..T3A spelled apart from the dense instances' below: one body for both compiles the dense ones differently)
+                // PE(x'), PE(w) feed T0 and, re-injected, the skip layer T3A.  The trunk part of a fused tile holds no ray direction or grid
+                // blocks, so in the fine pass the 24 registers can stay live through T1, T2 and the encodings be built once per tile (a build
+                // is ~1,000 VALU instructions per wave, and all eight waves run it at the same moment, the matrix pipe idle).  Measured per
+                // launch (W512 frame, LAB_NOTES.md): -1.3 % for the fine trunk; for FIELD_ALL_FUSED, whose tile also runs the deformation
+                // nets, the -0.8 % is below that launch's own spread, and it keeps the rebuild like the dense instances.
+                constexpr bool ENC_ONCE = MODE == FIELD_RADIANCE_FUSED;
                 f32x4 in_tr[KB_XYZ + KB_AMB];
-                auto build_enc = [&]() {
-                    const float xw[3] = {stash[0], stash[1], stash[2]}, amb[2] = {stash[3], stash[4]};
-                    if constexpr (DIAG_NOENC) {
-                        diag_blocks<KB_XYZ>(xw, q, in_tr);
-                        diag_blocks<KB_AMB>(amb, q, in_tr + KB_XYZ);
-                    } else {
-                        pe_blocks<3, L_XYZ, KB_XYZ>(xw, q, in_tr);
-#if SAHS_MODEL != 2
-                        pe_blocks<AMB_DIM, L_AMB, KB_AMB, AMB_INC>(amb, q, in_tr + KB_XYZ);
-#else
-                        (void)amb;
-#endif
-                    }
-                };
+                auto build_enc = [&]() { trunk_encodings(stash, q, in_tr); };
                 build_enc();
                 dense<KB_XYZ, KB_AMB, 16, CHF(L_T1)>(cx, in_tr, in_tr + KB_XYZ, h, Ly[L_T0].bias_off, false, 0.01f);
-                if constexpr (FUSED) {
-                    if (do_branch) b_hdr = sp.hdr[b_slot];
-                }
+                if (do_branch) b_hdr = sp.hdr[b_slot];
                 dense<16, 0, 16, CHF(L_T2)>(cx, h, nullptr, feat, Ly[L_T1].bias_off, false, 0.01f);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) h[i] = feat[i];
@@ -529,13 +472,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             } else {
             {
                 f32x4 in_tr[KB_XYZ + KB_AMB];
-                const float xw[3] = {stash[0], stash[1], stash[2]}, amb[2] = {stash[3], stash[4]};
-                pe_blocks<3, L_XYZ, KB_XYZ>(xw, q, in_tr);
-#if SAHS_MODEL != 2
-                pe_blocks<AMB_DIM, L_AMB, KB_AMB, AMB_INC>(amb, q, in_tr + KB_XYZ);
-#else
-                (void)amb;
-#endif
+                trunk_encodings(stash, q, in_tr);
                 if (sv_on) {
 #pragma unroll
                     for (int b = 0; b < KB_XYZ + KB_AMB; ++b)
@@ -555,13 +492,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             {   // skip layer: the re-injected encoding is rebuilt here instead of staying live (24 VGPRs) through T1, T2 -- registers the dense
                 // instances (237-245 VGPRs) do not have; the fine trunk above does, and builds it once
                 f32x4 in_tr[KB_XYZ + KB_AMB];
-                const float xw[3] = {stash[0], stash[1], stash[2]}, amb[2] = {stash[3], stash[4]};
-                pe_blocks<3, L_XYZ, KB_XYZ>(xw, q, in_tr);
-#if SAHS_MODEL != 2
-                pe_blocks<AMB_DIM, L_AMB, KB_AMB, AMB_INC>(amb, q, in_tr + KB_XYZ);
-#else
-                (void)amb;
-#endif
+                trunk_encodings(stash, q, in_tr);
                 dense<KB_XYZ, KB_AMB, 16, CHF(L_T3A)>(cx, in_tr, in_tr + KB_XYZ, feat, Ly[L_T3B].bias_off, false, 1.0f);
             }
             }
@@ -585,21 +516,23 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             dense_sv<SAVE, 16, 0, 16, CHF(L_ALPHA)>(cx, h, nullptr, feat, Ly[L_FEAT].bias_off, false, 1.0f, SV(act::FEAT, 256));
             if (dump) dsl[13] = feat[0][0];
         }
-        if constexpr (FUSED) {      // (a uniform two-way copy of this one-tile layer: NEXT is a compile-time size)
-            if (has_tile) {
-                if (do_branch) dense<16, 0, 1, CHF(L_D0B)>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
-                else dense<16, 0, 1, CHF(L_START)>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
-            }
-        } else if constexpr (!BRANCH) dense<16, 0, 1, (TRUNK ? CHF(L_START) : CHF(L_D0B))>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+        // fc_alpha -> FINAL tile.  What it prefetches: the branches' first chunk, or the first layer's when a fused tile wraps behind it (a
+        // uniform two-way copy of this one-tile layer: NEXT is a compile-time size).  (A block of its own: inside the trunk's, the fused
+        // instances compile differently.)
+        if (!FUSED || has_tile) {
+            if (FUSED && !do_branch) dense<16, 0, 1, CHF(L_START)>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+            else dense<16, 0, 1, CHF(L_D0B)>(cx, feat, nullptr, fin, Ly[L_ALPHA].bias_off, false, 1.0f);
+        }
         if constexpr (FUSED) {
             if (has_tile) {
                 if (p_raw < P) *reinterpret_cast<f32x4 *>(raw + p * D_RAW + 4 * q) = fin[0];
-                // live: the same expression as the trunk instances' below
+                // live: the composite will give the sample a weight that can be non-zero (render_ops.hip: sg = max(sigma + noise, 0), the same
+                // float expression; the last sample of a ray always has a weight, but with a background prior its channels are replaced)
                 const long ray = p / S;
                 const bool last = (p - ray * S) == S - 1;
-                const float sg = fin[0][3] + (sp.noise != nullptr ? sp.noise[p] : 0.0f);
+                const float sg = fin[0][3] + (sp.noise != nullptr ? sp.noise[p] : 0.0f);      // sigma: row 15 = value 3 of the q == 3 lanes
                 const bool live = q == 3 && p_raw < P && (last ? sp.has_bg == 0 : sg > 0.0f);
-                const uint32_t mask = (uint32_t)(__ballot(live) >> 48);
+                const uint32_t mask = (uint32_t)(__ballot(live) >> 48);      // bit j: column j of this wave's 16 samples
                 // slots: the waves' live counts through LDS (read again only after the many chunk barriers of the next tile)
                 uint32_t *cnts = reinterpret_cast<uint32_t *>(lds + LDS_TOTAL_FLOATS);
                 if (cx.lane == 0) cnts[cx.wave] = (uint32_t)__popc(mask);
@@ -629,7 +562,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
                 r_total += all;
             }
             if (!do_branch) continue;      // the stream has wrapped to the first layer
-            // the branch pass: x' -> stash, the FINAL tile behind fc_alpha from the raw row, feat from the record (as FIELD_BRANCH)
+            // the branch pass: x' -> stash (w is not needed behind the trunk), the FINAL tile behind fc_alpha from the raw row, feat from the record
             smp = __float_as_int(b_hdr[3]);
             __builtin_amdgcn_wave_barrier();
             if (q == 0) { stash[0] = b_hdr[0]; stash[1] = b_hdr[1]; stash[2] = b_hdr[2]; }
@@ -642,49 +575,15 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             r_head += (uint32_t)F32_PTS_PER_WG;
             if (r_head >= r_cap) r_head -= r_cap;
         }
-        if constexpr (TRUNK) {
-            if (p_raw < P) *reinterpret_cast<f32x4 *>(raw + p * D_RAW + 4 * q) = fin[0];
-            // live: the composite will give the sample a weight that can be non-zero (render_ops.hip: sg = max(sigma + noise, 0), the same
-            // float expression; the last sample of a ray always has a weight, but with a background prior its channels are replaced)
-            const long ray = p / S;
-            const bool last = (p - ray * S) == S - 1;
-            const float sg = fin[0][3] + (sp.noise != nullptr ? sp.noise[p] : 0.0f);      // sigma: row 15 = value 3 of the q == 3 lanes
-            const bool live = q == 3 && p_raw < P && (last ? sp.has_bg == 0 : sg > 0.0f);
-            const uint32_t mask = (uint32_t)(__ballot(live) >> 48);      // bit j: column j of this wave's 16 samples
-            if (!DIAG_NOAPPEND && mask != 0u) {
-                uint32_t base = 0u;
-                if (cx.lane == 0) base = atomicAdd(sp.count, (unsigned int)__popc(mask));
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                const int j = cx.lane & 15;
-                const uint32_t slot = base + (uint32_t)__popc(mask & ((1u << j) - 1u));
-                if (((mask >> j) & 1u) && slot < sp.cap) {
-                    f32x4 *rec = sp.feat + (long)(slot >> 4) * (16 * 64) + q * 16 + (slot & 15u);
-#pragma unroll
-                    for (int b = 0; b < 16; ++b) rec[b * 64] = feat[b];
-                    if (q == 0) sp.hdr[slot] = f32x4{stash[0], stash[1], stash[2], __int_as_float((int)p)};
-                }
-            }
-            continue;      // the stream has wrapped to this launch's first layer
-        }
         if (dbg != nullptr && p_raw < P) *reinterpret_cast<f32x4 *>(dsl + 24 + 4 * q) = fin[0];
         // ---- colour branch (modules.py:276-287) ----
         {
             f32x4 in_d[4];
             {
-                if constexpr (BRANCH && DIAG_NOLOADS_BRANCH) {
-                    pe_blocks<3, 4, 2>(x, q, in_d);
-                    diag_blocks<2>(x, q, in_d + 2);
-                } else if constexpr (BRANCH && DIAG_NOENC) {
-                    const float *rp = rays + (smp / S) * ray_stride;
-                    const float rd[3] = {rp[3], rp[4], rp[5]};
-                    diag_blocks<2>(rd, q, in_d);
-                    grid_blocks(grid, stash[0], stash[1], stash[2], q, in_d + 2);
-                } else {
                 const float *rp = rays + (smp / S) * ray_stride;
                 const float rd[3] = {rp[3], rp[4], rp[5]};
                 pe_blocks<3, 4, 2>(rd, q, in_d);                                  // models.py:340 (raw, un-normalised direction)
                 grid_blocks(grid, stash[0], stash[1], stash[2], q, in_d + 2);     // models.py:525
-                }
                 if (sv_on) {
 #pragma unroll
                     for (int b = 0; b < 4; ++b) *reinterpret_cast<f32x4 *>(b < 2 ? SVP(act::DIR, 32) + 16 * b : SVP(act::GRID, 32) + 16 * (b - 2)) = in_d[b];
@@ -728,7 +627,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         if (FUSED ? (uint32_t)(cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15)) < b_valid : p_raw < P)
             *reinterpret_cast<f32x4 *>(raw + smp * D_RAW + 4 * q) = fin[0];   // cat((rgb, seg, alpha)) modules.py:295
     }
-    if constexpr (FUSED) {      // the pass's live count, once per workgroup (no value returned); the second head word says which path ran
+    if constexpr (FUSED) {      // the pass's live count, once per workgroup (no value returned); the second head word: a sparse pass ran
         if (threadIdx.x == 0) {
             if (r_total != 0u) atomicAdd(sp.count, r_total);
             if (blockIdx.x == 0) sp.count[1] = 1u;
@@ -814,14 +713,12 @@ extern "C" int SAHS_SYM(sahs_field_forward_f32_split_bits_launch)(const float *p
 #endif
 }
 
-// The sparse branches (see the kernel's MODE).  stage 0: FIELD_ALL_TRUNK over (rays, zvals), x', w also written to xw when given; stage 1:
-// FIELD_RADIANCE_TRUNK on x', w fetched from xw through src; stage 2: FIELD_BRANCH over the records the trunk launch appended.
-// ws: sahs_field_f32_sparse_ws_bytes(cap) bytes, 16-byte aligned: [record count, zeroed by the caller before the trunk launch | headers |
-// feat groups]; cap: record slots, a multiple of 128 and at least P (every sample may be live).  noise / has_bg: the composite's noise of
-// these samples (or null) and whether it is given a background prior -- what decides which samples are live.
-// The fused instances (see the kernel's MODE): stage 3 = FIELD_ALL_FUSED, stage 4 = FIELD_RADIANCE_FUSED, one launch for the whole pass; the
-// workspace then holds the workgroups' rings, sahs_field_f32_sparse_ring_slots(P, num_cu) slots (never more than P rounded up to 128), and
-// cap only has to cover those.  The launch adds the pass's live count to the head's first word and sets its second word to 1.
+// The sparse branches (see the kernel's MODE), one launch for the whole pass.  stage 0: FIELD_ALL_FUSED over (rays, zvals), x', w also
+// written to xw when given; stage 1: FIELD_RADIANCE_FUSED on x', w fetched from xw through src.
+// ws: sahs_field_f32_sparse_ws_bytes(cap) bytes, 16-byte aligned: [head: two words, zeroed by the caller | headers | feat groups]; cap:
+// record slots, a multiple of 128 and at least the workgroups' rings, sahs_field_f32_sparse_ring_slots(P, num_cu) (never more than P
+// rounded up to 128).  noise / has_bg: the composite's noise of these samples (or null) and whether it is given a background prior --
+// what decides which samples are live.  The launch adds the pass's live count to the head's first word and sets its second word to 1.
 extern "C" long SAHS_SYM(sahs_field_f32_sparse_ws_bytes)(long cap) { return SPARSE_HEAD_BYTES + cap * SPARSE_RECORD_BYTES; }
 extern "C" long SAHS_SYM(sahs_field_f32_sparse_ring_slots)(long P, int num_cu)
 {
@@ -835,22 +732,15 @@ extern "C" int SAHS_SYM(sahs_field_forward_f32_sparse_launch)(const float *packe
                                                     hipStream_t stream)
 {
     if (P <= 0) return 0;
-    const bool fused = stage == 3 || stage == 4;
     if (ws == nullptr || cap % F32_PTS_PER_WG != 0 || cap > (1L << 30)) return -4;
-    if (cap < (fused ? SAHS_SYM(sahs_field_f32_sparse_ring_slots)(P, num_cu) : P)) return -4;
+    if (cap < SAHS_SYM(sahs_field_f32_sparse_ring_slots)(P, num_cu)) return -4;
     char *base = static_cast<char *>(ws);
     SparseArgs sp{noise, reinterpret_cast<unsigned int *>(base), reinterpret_cast<f32x4 *>(base + SPARSE_HEAD_BYTES),
                   reinterpret_cast<f32x4 *>(base + SPARSE_HEAD_BYTES + cap * 16), (unsigned int)cap, has_bg};
     if (stage == 0)
-        return launch_field<false, FIELD_ALL_TRUNK>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream, nullptr, sp);
-    if (stage == 2)      // (P: an upper bound of the record count, for the grid)
-        return launch_field<false, FIELD_BRANCH>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, nullptr, 0, 0, nullptr, num_cu, stream, nullptr, sp);
-    if (stage == 3)
         return launch_field<false, FIELD_ALL_FUSED>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream, nullptr, sp);
 #if SAHS_MODEL != 2
     if (stage == 1)
-        return launch_field<false, FIELD_RADIANCE_TRUNK>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, xw, xw_row, 0, src, num_cu, stream, nullptr, sp);
-    if (stage == 4)
         return launch_field<false, FIELD_RADIANCE_FUSED>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, xw, xw_row, 0, src, num_cu, stream, nullptr, sp);
 #endif
     return -2;

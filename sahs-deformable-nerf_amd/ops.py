@@ -266,57 +266,39 @@ def render_rays(packed, frame, rays, num_coarse, num_fine, precision=SAHS_F32, l
     return rgb_c, disp_c, acc_c, None, None, None, w_bg, depth_f
 
 
-# upper bound of the record workspace of the sparse branches.  None: what the one-launch (fused) form of a pass of any size needs on the
-# current device -- the record rings of its persistent workgroups, asked of the library (0.13 GiB on a 256-CU MI355X).  A render whose
-# workspace holds less than its rings runs trunk + branch launches over ray slabs instead (W512 frame, LAB_NOTES.md: 4 GiB of records =
-# 3 + 5 slabs per 131,072-ray chunk)
-_SPARSE_WORKSPACE_BYTES = None
 _SPARSE_BRANCHES = True
+_SPARSE_MAX_SAMPLES = 1 << 30      # a record's header holds the sample index as an int: a larger pass renders dense
 
 
-def sparse_branches(on=None, workspace_bytes=None):
+def sparse_branches(on=None):
     """The fp32 inference render (render_rays_rows) skips the colour and seg branches of samples the composite gives the weight exactly 0
     (sigma + noise <= 0; with a background prior also the last sample of a ray): include/sahs_nerf.h, sahs_model_render_rays_rows_sparse.
     The rendered rows are bit-identical either way; in the `raw` workspace columns 0..14 of a zero-weight sample then hold the output
-    biases, not its logits.  sparse_branches(False) keeps the dense launches (the A/B reference).  workspace_bytes: upper bound of the
-    record workspace a render allocates (it never takes more than one slab of the chunk's fine pass needs; sparse_workspace_bytes() queries
-    it).  The default is what the fused form -- one launch per pass -- needs; a smaller bound selects the slab form (sparse_last_path tells
-    which one ran).  None queries -> bool."""
-    global _SPARSE_BRANCHES, _SPARSE_WORKSPACE_BYTES
+    biases, not its logits.  sparse_branches(False) keeps the dense launches (the A/B reference).  None queries -> bool."""
+    global _SPARSE_BRANCHES
     if on is not None:
         if not isinstance(on, (bool, int)) or on not in (0, 1, False, True):
             raise _lib.SahsError("sparse_branches: True or False, not %r" % (on,))
         _SPARSE_BRANCHES = bool(on)
-    if workspace_bytes is not None:
-        if not isinstance(workspace_bytes, int) or isinstance(workspace_bytes, bool) or workspace_bytes < 1:
-            raise _lib.SahsError("sparse_branches: workspace_bytes must be a positive int, not %r" % (workspace_bytes,))
-        _SPARSE_WORKSPACE_BYTES = workspace_bytes
     return _SPARSE_BRANCHES
 
 
-def sparse_workspace_bytes():
-    """The upper bound of the sparse branches' record workspace (sparse_branches(workspace_bytes=...))."""
-    if _SPARSE_WORKSPACE_BYTES is None:      # (the ring size does not depend on the model; the largest pass the library sizes)
-        return int(_lib.lib().sahs_model_render_sparse_fused_workspace_bytes(0, 1 << 30))
-    return _SPARSE_WORKSPACE_BYTES
+def _sparse_head(workspace, who):
+    rec = workspace.get("sparse") if workspace else None
+    if rec is None:
+        raise _lib.SahsError("%s: this workspace has not been through a sparse render" % who)
+    return rec[:8].view(torch.int32)
 
 
 def sparse_last_count(workspace):
-    """Live records the last appending launch of a render_rays_rows call counted (fused: its whole last pass; slabs: the last slab of its
-    last pass), read back from the record workspace kept in ``workspace``: a measurement aid -- it synchronises."""
-    rec = workspace.get("sparse") if workspace else None
-    if rec is None:
-        raise _lib.SahsError("sparse_last_count: this workspace has not been through a sparse render")
-    return int(rec[:4].view(torch.int32).item())
+    """Live records the last pass of a render_rays_rows call counted, read back from the record workspace kept in ``workspace``: a
+    measurement aid -- it synchronises."""
+    return int(_sparse_head(workspace, "sparse_last_count")[0].item())
 
 
 def sparse_last_path(workspace):
-    """1 if the last pass of a render_rays_rows call through ``workspace`` ran fused (one launch, per-workgroup record rings), 0 if it ran as
-    trunk + branch launches over slabs: a measurement aid like sparse_last_count -- it synchronises."""
-    rec = workspace.get("sparse") if workspace else None
-    if rec is None:
-        raise _lib.SahsError("sparse_last_path: this workspace has not been through a sparse render")
-    return int(rec[4:8].view(torch.int32).item())
+    """1 once a sparse pass ran through ``workspace`` (the second head word of its record workspace); it synchronises."""
+    return int(_sparse_head(workspace, "sparse_last_path")[1].item())
 
 
 ROW_COLUMNS = 36      # SAHS_ROW_* of include/sahs_nerf.h: rgb_c 0:15, disp_c 15, acc_c 16, rgb_f 17:32, disp_f 32, acc_f 33, w_bg 34, depth_f 35
@@ -361,10 +343,10 @@ def render_rays_rows(packed, frame, rays, num_coarse, num_fine, rows, precision=
         xw, z_new = buf("xw", N, Sf, 8), buf("z_new", N, num_fine)
         src = _workspace_buffer(ws, dev, "src", (N, Sf), torch.int32)
     extra = []
-    if _SPARSE_BRANCHES and precision == SAHS_F32 and N > 0:
-        # record workspace of the sparse branches: what the fine pass needs in one slab, capped (a smaller one means more slabs)
-        # (the size query answers up to 2^30 samples; a larger pass is cut into slabs anyway)
-        want = min(int(_fn("render_sparse_workspace_bytes", arch)[0](min(N * Sf, 1 << 30))), sparse_workspace_bytes())
+    if _SPARSE_BRANCHES and precision == SAHS_F32 and 0 < N * Sf <= _SPARSE_MAX_SAMPLES:
+        # record workspace of the sparse branches: the workgroups' rings of the fine pass (N * Sf samples).  They cover the coarse pass
+        # too: the ring slots of a pass never go down as its samples go up (csrc/field_f32.hip: sparse_ring_base)
+        want = int(_fn("render_sparse_fused_workspace_bytes", arch)[0](N * Sf))
         extra = [_p(_workspace_buffer(ws, dev, "sparse", (want,), torch.uint8)), want]
     f, name = _fn("render_rays_rows_sparse" if extra else "render_rays_rows", arch)
     check(f(_p(packed), _p(frame), precision, N, _p(rays), int(rays.shape[1]), int(num_coarse), int(num_fine),

@@ -22,12 +22,6 @@ VARIANTS = {"base": ["SAHS_DIAG"],
             "x3floor": ["SAHS_DIAG", "SAHS_X3_NODMA", "SAHS_X3_NOBARRIER", "SAHS_X3_NOAREAD"],
             # the backward chain kernels (csrc/field_bwd_chain.hip): what they wait for (tools/ab_chain.sh runs them under rocprofv3)
             "cnostore": ["SAHS_DIAG", "SAHS_BWC_NOSTORE"], "cnogstore": ["SAHS_DIAG", "SAHS_BWC_NOGSTORE"], "ctilemajor": ["SAHS_DIAG", "SAHS_BWC_TILEMAJOR"], "cplainstore": ["SAHS_DIAG", "SAHS_BWC_PLAINSTORE"],
-            # the sparse instances of the fp32 field kernel (csrc/field_f32.hip: field_forward_f32_kernel<false, 3|4|5>), timed per kernel under
-            # rocprofv3 on bench.py with SAHS_NERF_LIB=<variant> (tools/ab_sparse.sh): the encodings built again before the skip layer (as before the fine trunk
-            # kept them live) / none at all / the tile prologue's loads replaced by made-up values / no record append.  A made-up sigma changes the
-            # live count, so the trunk's loads are priced without the append on both sides: f32noappend against f32noappend_noloads
-            "f32enc2": ["SAHS_DIAG", "SAHS_F32_ENC2"], "f32noenc": ["SAHS_DIAG", "SAHS_F32_NOENC"], "f32noappend": ["SAHS_DIAG", "SAHS_F32_NOAPPEND"],
-            "f32noappend_noloads": ["SAHS_DIAG", "SAHS_F32_NOAPPEND", "SAHS_F32_NOLOADS_TRUNK"], "f32branch_noloads": ["SAHS_DIAG", "SAHS_F32_NOLOADS_BRANCH"],
             "cnomask": ["SAHS_DIAG", "SAHS_BWC_NOMASK"], "cnostore_nomask": ["SAHS_DIAG", "SAHS_BWC_NOSTORE", "SAHS_BWC_NOMASK"]}
 
 
