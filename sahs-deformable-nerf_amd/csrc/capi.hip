@@ -130,6 +130,25 @@ int sahs_stratified_depths(long N, int S, const float *rays, int ray_stride, int
     return e ? hip_fail("sahs_stratified_depths", e) : 0;
 }
 
+// Where one composite writes its maps: as separate tensors (rgb rows of 15 floats, scalars contiguous), or as the coarse / fine columns of
+// a rows buffer (include/sahs_nerf.h: SAHS_ROW_*).  depth and w_last may be null (a coarse pass that a fine pass follows writes neither).
+struct CompositeOut {
+    float *rgb, *disp, *acc, *depth, *w_last;
+    int rgb_ld, sc_ld;
+};
+static CompositeOut composite_tensors(float *rgb, float *disp, float *acc, float *depth, float *w_last) { return {rgb, disp, acc, depth, w_last, 15, 1}; }
+static CompositeOut composite_rows(float *rows, int row_ld, bool fine)
+{
+    if (fine) return {rows + SAHS_ROW_RGB_F, rows + SAHS_ROW_DISP_F, rows + SAHS_ROW_ACC_F, rows + SAHS_ROW_DEPTH_F, rows + SAHS_ROW_W_BG, row_ld, row_ld};
+    return {rows + SAHS_ROW_RGB_C, rows + SAHS_ROW_DISP_C, rows + SAHS_ROW_ACC_C, nullptr, nullptr, row_ld, row_ld};
+}
+static int composite_launch(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise, const float *bg,
+                            int white_background, float *weights, const CompositeOut &o, hipStream_t st)
+{
+    return sahs_composite_forward_launch(N, S, raw, z, rays, ray_stride, noise, bg, white_background, o.rgb, o.disp, o.acc, weights, o.depth, o.w_last,
+                                         o.rgb_ld, o.sc_ld, st);
+}
+
 int sahs_composite_forward(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
                            const float *bg, int white_background, float *rgb, float *disp, float *acc, float *weights, float *depth,
                            void *stream)
@@ -137,8 +156,8 @@ int sahs_composite_forward(long N, int S, const float *raw, const float *z, cons
     if (N == 0) return 0;
     REQUIRE(raw && z && rays && rgb && disp && acc && weights && depth && ray_stride >= 6, "sahs_composite_forward");
     REQUIRE(N >= 0 && S >= 1 && S <= 256 && ALIGNED16(raw), "sahs_composite_forward(shape: 1 <= S <= 256)");
-    int e = sahs_composite_forward_launch(N, S, raw, z, rays, ray_stride, noise, bg, white_background, rgb, disp, acc, weights, depth,
-                                          nullptr, 15, 1, (hipStream_t)stream);
+    int e = composite_launch(N, S, raw, z, rays, ray_stride, noise, bg, white_background, weights, composite_tensors(rgb, disp, acc, depth, nullptr),
+                             (hipStream_t)stream);
     return e ? hip_fail("sahs_composite_forward", e) : 0;
 }
 
@@ -274,18 +293,15 @@ int sahs_composite_forward_rows(long N, int S, const float *raw, const float *z,
     if (N == 0) return 0;
     REQUIRE(raw && z && rays && weights && rows && ray_stride >= 6 && row_ld >= SAHS_ROW_COLUMNS, "sahs_composite_forward_rows");
     REQUIRE(N >= 0 && S >= 1 && S <= 256 && ALIGNED16(raw), "sahs_composite_forward_rows(shape: 1 <= S <= 256)");
-    int e = fine_pass ? sahs_composite_forward_launch(N, S, raw, z, rays, ray_stride, noise, bg, white_background, rows + SAHS_ROW_RGB_F,
-                                                      rows + SAHS_ROW_DISP_F, rows + SAHS_ROW_ACC_F, weights, rows + SAHS_ROW_DEPTH_F,
-                                                      rows + SAHS_ROW_W_BG, row_ld, row_ld, (hipStream_t)stream)
-                      : sahs_composite_forward_launch(N, S, raw, z, rays, ray_stride, noise, bg, white_background, rows + SAHS_ROW_RGB_C,
-                                                      rows + SAHS_ROW_DISP_C, rows + SAHS_ROW_ACC_C, weights, nullptr, nullptr, row_ld,
-                                                      row_ld, (hipStream_t)stream);
+    int e = composite_launch(N, S, raw, z, rays, ray_stride, noise, bg, white_background, weights, composite_rows(rows, row_ld, fine_pass != 0),
+                             (hipStream_t)stream);
     return e ? hip_fail("sahs_composite_forward_rows", e) : 0;
 }
 
 // ---- every built architecture in one table row: the per-model entries the ABI reaches (nullptr: that model's build has none) ----
 // model: SAHS_MODEL_AUDIO, SAHS_MODEL_NERFACE (config/expression/person_2|3.yml),
 // SAHS_MODEL_NERFACE_STATIC (config/expression/person_1.yml: no warp, no hyper sheet).
+enum Kernel { K_NONE, K_F32, K_BF16, K_X3 };         // the field kernel a launch runs on (ModelFns::field)
 enum Pack { PK_NONE, PK_F32, PK_BF16, PK_X3 };      // the weight packings of a model build (pack.hip): fp32, bf16 stream, hi/lo streams
 typedef int (*pack_fn)(const float *, float *, hipStream_t);
 struct ModelFns {
@@ -302,12 +318,10 @@ struct ModelFns {
     int (*fold)(const float *, const float *, const float *, int, float *, hipStream_t);
     int (*bwd_gemm_precision_state)(int);
     int (*bf16w_exact_leaky_state)(int);
-    // fp32 field kernel (field_f32.hip): whole network, split evaluation, split evaluation writing sign-bit planes
-    decltype(&sahs_field_forward_f32_launch) f32;
-    decltype(&sahs_field_forward_f32_split_launch) f32_split;
-    decltype(&sahs_field_forward_f32_split_bits_launch) f32_split_bits;
+    // the field forward of each Kernel (field_f32.hip, field_bf16w.hip, field_bf16x3.hip): a FieldLaunch and its mode
+    int (*field[4])(const FieldLaunch *, int);
     // ... and the inference render's sparse branches: the one-launch pass, the bytes of a record workspace and the slots a pass's rings need
-    decltype(&sahs_field_forward_f32_sparse_launch) f32_sparse;
+    decltype(&sahs_field_f32_sparse_launch) f32_sparse;
     decltype(&sahs_field_f32_sparse_ws_bytes) f32_sparse_ws_bytes;
     decltype(&sahs_field_f32_sparse_ring_slots) f32_sparse_ring_slots;
     // backward (field_bwd.hip): per-layer walk, cut at the (x', w) seam, fused walk
@@ -316,16 +330,6 @@ struct ModelFns {
     decltype(&sahs_field_backward_split_launch) bwd_split;
     long (*fused_ws_words)(int, long);
     decltype(&sahs_field_backward_fused_launch) bwd_fused;
-    // bf16 field kernel (field_bf16w.hip): whole network, split evaluation
-    decltype(&sahs_field_forward_bf16w_launch) bf16w;
-    decltype(&sahs_field_forward_bf16w_split_launch) bf16w_split;
-    // split-operand kernels (field_bf16x3.hip): deformation and radiance launches of the split chain, and the whole network
-    decltype(&sahs_field_deform_bf16x3_launch) deform_x3;
-    decltype(&sahs_field_deform_bf16x3_save_launch) deform_x3_save;
-    decltype(&sahs_field_radiance_bf16x3_launch) radiance_x3;
-    decltype(&sahs_field_radiance_bf16x3_save_launch) radiance_x3_save;
-    decltype(&sahs_field_forward_bf16x3_launch) x3;
-    decltype(&sahs_field_forward_bf16x3_save_launch) x3_save;
 };
 #define SAHS_MODEL_ROW(sfx, deform)                                                                                                    \
     deform, sahs_layout_param_count##sfx, sahs_layout_frame_words##sfx, sahs_layout_act_words##sfx,                                 \
@@ -333,23 +337,14 @@ struct ModelFns {
         {nullptr, sahs_pack_weights_f32_launch##sfx, sahs_pack_weights_bf16_launch##sfx, sahs_pack_weights_bf16x3_launch##sfx},      \
         sahs_layout_executed_macs##sfx, sahs_layout_act_part_words##sfx, sahs_layout_act_part_col0##sfx, sahs_layout_bits_part_words##sfx, \
         sahs_fold_conditioning_launch##sfx, sahs_bwd_gemm_precision_state##sfx, sahs_bf16w_exact_leaky_state##sfx,                  \
-        sahs_field_forward_f32_launch##sfx, sahs_field_forward_f32_split_launch##sfx, sahs_field_forward_f32_split_bits_launch##sfx, \
-        sahs_field_forward_f32_sparse_launch##sfx, sahs_field_f32_sparse_ws_bytes##sfx, sahs_field_f32_sparse_ring_slots##sfx,       \
+        {nullptr, sahs_field_f32_launch##sfx, sahs_field_bf16w_launch##sfx, sahs_field_bf16x3_launch##sfx},                          \
+        sahs_field_f32_sparse_launch##sfx, sahs_field_f32_sparse_ws_bytes##sfx, sahs_field_f32_sparse_ring_slots##sfx,               \
         sahs_field_backward_ws_words##sfx, sahs_field_backward_launch##sfx, sahs_field_backward_split_launch##sfx,                  \
         sahs_field_backward_fused_ws_words##sfx, sahs_field_backward_fused_launch##sfx
-static const ModelFns kModels[3] = {
-    // ..., bf16w, bf16w_split, deform_x3, deform_x3_save, radiance_x3, radiance_x3_save, x3, x3_save
-    {SAHS_MODEL_ROW(, true), sahs_field_forward_bf16w_launch, sahs_field_forward_bf16w_split_launch, sahs_field_deform_bf16x3_launch,
-     sahs_field_deform_bf16x3_save_launch, sahs_field_radiance_bf16x3_launch, sahs_field_radiance_bf16x3_save_launch, nullptr, nullptr},
-    {SAHS_MODEL_ROW(_nf, true), nullptr, sahs_field_forward_bf16w_split_launch_nf, sahs_field_deform_bf16x3_launch_nf,
-     sahs_field_deform_bf16x3_save_launch_nf, sahs_field_radiance_bf16x3_launch_nf, sahs_field_radiance_bf16x3_save_launch_nf, nullptr, nullptr},
-    {SAHS_MODEL_ROW(_ns, false), sahs_field_forward_bf16w_launch_ns, nullptr, nullptr, nullptr, nullptr, nullptr,
-     sahs_field_forward_bf16x3_launch_ns, sahs_field_forward_bf16x3_save_launch_ns},
-};
+static const ModelFns kModels[3] = {{SAHS_MODEL_ROW(, true)}, {SAHS_MODEL_ROW(_nf, true)}, {SAHS_MODEL_ROW(_ns, false)}};
 #undef SAHS_MODEL_ROW
 
 // ---- every (model, precision) pair, described once ----
-enum Kernel { K_NONE, K_F32, K_BF16, K_X3 };         // the field kernel a launch runs on
 struct Pipe {
     Pack seg[3];        // the packed buffer: these packings back to back from word 0, each at a 16-byte boundary (none: not built)
     Kernel whole;       // the whole-network launch (sahs_model_field_forward); K_NONE: the pair exists only as the split chain
@@ -505,14 +500,10 @@ static int field_forward(const char *who, int model, const void *packed, const f
     if (p->whole == K_NONE)
         return fail(2, "%s: precision %d of this model runs through sahs_model_field_forward_split / sahs_model_render_rays_rows (it needs the "
                        "xw workspace)", who, precision);
-    const ModelFns &m = kModels[model];
-    const float *pk = (const float *)packed;
     hipStream_t st = (hipStream_t)stream;
-    int e = probed(probe_kind(model, precision, level, 0), N * S, st, [&] {
-        if (p->whole == K_F32) return m.f32(pk, frame, level, N * S, S, rays, ray_stride, z, raw, dbg, nullptr, num_cus(), st);
-        if (p->whole == K_BF16) return m.bf16w(pk, frame, level, N * S, S, rays, ray_stride, z, raw, dbg, num_cus(), st);
-        return m.x3(pk, frame, level, N * S, S, rays, ray_stride, z, raw, num_cus(), st);      // (no debug planes)
-    });
+    const FieldLaunch L{.packed = (const float *)packed, .frame = frame, .level = level, .P = N * S, .S = S, .rays = rays, .ray_stride = ray_stride,
+                        .zvals = z, .raw = raw, .dbg = dbg, .num_cu = num_cus(), .stream = st};      // (the split-operand kernels have no debug planes)
+    int e = probed(probe_kind(model, precision, level, 0), N * S, st, [&] { return kModels[model].field[p->whole](&L, 0); });
     return e ? hip_fail(who, e) : 0;
 }
 int sahs_field_forward(const void *packed, const float *frame, int level, long N, int S, const float *rays, int ray_stride,
@@ -525,56 +516,6 @@ int sahs_model_field_forward(int model, const void *packed, const float *frame, 
 {
     REQUIRE_MODEL(model, "sahs_model_field_forward");
     return field_forward("sahs_model_field_forward", model, packed, frame, level, N, S, rays, ray_stride, z, raw, dbg, precision, stream);
-}
-
-static int render_rays_chain(const char *who, int model, const void *packed, const float *frame, int precision, long N,
-                             const float *rays, int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg,
-                             const float *t_rand, const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f,
-                             float *raw, float *weights, float *rgb_c, float *disp_c, float *acc_c, float *rgb_f, float *disp_f,
-                             float *acc_f, float *w_bg, float *depth_f, void *stream, int rgb_ld = 15, int sc_ld = 1)
-{
-    if (N == 0) return 0;   // an empty ray chunk: nothing to launch (its tensors have null data pointers)
-    REQUIRE(packed && frame && rays && z_c && raw && weights && rgb_c && disp_c && acc_c && w_bg && depth_f, who);
-    REQUIRE(nf == 0 || (z_f && rgb_f && disp_f && acc_f), who);
-    hipStream_t st = (hipStream_t)stream;
-    int e;
-    if ((e = sahs_stratified_depths(N, Sc, rays, ray_stride, lindisp, t_rand, z_c, stream))) return e;
-    if ((e = field_forward(who, model, packed, frame, 0, N, Sc, rays, ray_stride, z_c, raw, nullptr, precision, stream))) return e;
-    REQUIRE(Sc <= 256, who);
-    // the coarse depth is written only when there is no fine pass (the reference returns depth_fine only)
-    e = sahs_composite_forward_launch(N, Sc, raw, z_c, rays, ray_stride, noise_c, bg, white_background, rgb_c, disp_c, acc_c, weights,
-                                      nf == 0 ? depth_f : nullptr, nf == 0 ? w_bg : nullptr, rgb_ld, sc_ld, st);
-    if (e) return hip_fail(who, e);
-    if (nf > 0) {
-        const int Sf = Sc + nf;
-        REQUIRE(Sf <= 256, who);
-        if ((e = sahs_resample(N, Sc, nf, z_c, weights, u, nullptr, z_f, nullptr, stream))) return e;
-        if ((e = field_forward(who, model, packed, frame, 1, N, Sf, rays, ray_stride, z_f, raw, nullptr, precision, stream))) return e;
-        e = sahs_composite_forward_launch(N, Sf, raw, z_f, rays, ray_stride, noise_f, bg, white_background, rgb_f, disp_f, acc_f,
-                                          weights, depth_f, w_bg, rgb_ld, sc_ld, st);
-        if (e) return hip_fail(who, e);
-    }
-    return 0;
-}
-
-int sahs_render_rays(const void *packed, const float *frame, int precision, long N, const float *rays, int ray_stride, int Sc, int nf,
-                     int lindisp, int white_background, const float *bg, const float *t_rand, const float *noise_c, const float *u,
-                     const float *noise_f, float *z_c, float *z_f, float *raw, float *weights, float *rgb_c, float *disp_c,
-                     float *acc_c, float *rgb_f, float *disp_f, float *acc_f, float *w_bg, float *depth_f, void *stream)
-{
-    return render_rays_chain("sahs_render_rays", SAHS_MODEL_AUDIO, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp,
-                             white_background, bg, t_rand, noise_c, u, noise_f, z_c, z_f, raw, weights, rgb_c, disp_c, acc_c, rgb_f, disp_f,
-                             acc_f, w_bg, depth_f, stream);
-}
-int sahs_model_render_rays(int model, const void *packed, const float *frame, int precision, long N, const float *rays, int ray_stride,
-                           int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand, const float *noise_c,
-                           const float *u, const float *noise_f, float *z_c, float *z_f, float *raw, float *weights, float *rgb_c,
-                           float *disp_c, float *acc_c, float *rgb_f, float *disp_f, float *acc_f, float *w_bg, float *depth_f, void *stream)
-{
-    REQUIRE_MODEL(model, "sahs_model_render_rays");
-    return render_rays_chain("sahs_model_render_rays", model, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp, white_background,
-                             bg, t_rand, noise_c, u, noise_f, z_c, z_f, raw, weights, rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, w_bg, depth_f,
-                             stream);
 }
 
 /* The split evaluation of the field (csrc/field_f32.hip, MODE): 0 whole network + x', w written to xw; 1 deformation nets only;
@@ -597,35 +538,26 @@ int sahs_model_field_forward_split(int model, const void *packed, const float *f
     const float *pk = (const float *)packed;
     const long P = N * S;
     hipStream_t st = (hipStream_t)stream;
+    FieldLaunch L{.packed = pk, .frame = frame, .level = level, .P = P, .S = S, .rays = rays, .ray_stride = ray_stride, .zvals = z, .raw = raw,
+                  .xw = xw, .xw_row = xw_row, .xw_col0 = xw_col0, .src = mode == 2 ? src : nullptr, .num_cu = num_cus(), .stream = st};
     int e = 0;
     if (chain) {      // deformation launch, then radiance launch (mode 0 = both, one after the other)
         REQUIRE(mode != 0 || xw_col0 == 0, who);
         long off[4];
         packed_layout(model, p, off);
-        if (mode != 2 && !x3_deform_on_f32())
-            e = probed(probe_kind(model, SAHS_BF16X3, level, 1), P, st, [&] {
-                return m.deform_x3(pk + off[PK_X3], frame, level, P, S, rays, ray_stride, z, xw, xw_row, xw_col0, num_cus(), st);
-            });
-        else if (mode != 2)
-            e = probed(probe_kind(model, SAHS_F32, level, 1), P, st, [&] {
-                return m.f32_split(pk + off[PK_F32], frame, level, 1, P, S, rays, ray_stride, z, nullptr, xw, xw_row, xw_col0, nullptr, nullptr,
-                                   num_cus(), st);
-            });
-        if (!e && mode != 1)
-            e = probed(probe_kind(model, precision, level, 2), P, st, [&] {
-                const int *sp = mode == 2 ? src : nullptr;
-                return p->chain == K_BF16
-                           ? m.bf16w_split(pk + off[PK_BF16], frame, level, 2, P, S, rays, ray_stride, nullptr, raw, xw, xw_row, 0, sp, num_cus(), st)
-                           : m.radiance_x3(pk + off[PK_X3], frame, level, P, S, rays, ray_stride, raw, xw, xw_row, sp, num_cus(), st);
-            });
+        if (mode != 2) {
+            const bool f32 = x3_deform_on_f32();
+            L.packed = pk + off[f32 ? PK_F32 : PK_X3];
+            e = probed(probe_kind(model, f32 ? SAHS_F32 : SAHS_BF16X3, level, 1), P, st, [&] { return m.field[f32 ? K_F32 : K_X3](&L, 1); });
+        }
+        if (!e && mode != 1) {
+            L.packed = pk + off[p->chain == K_BF16 ? PK_BF16 : PK_X3];
+            e = probed(probe_kind(model, precision, level, 2), P, st, [&] { return m.field[p->chain](&L, 2); });
+        }
         return e ? hip_fail(who, e) : 0;
     }
     if (!p || p->split == K_NONE) return fail(4, "%s: precision %d is not built for this model", who, precision);
-    e = probed(probe_kind(model, precision, level, mode), P, st, [&] {
-        return p->split == K_BF16
-                   ? m.bf16w_split(pk, frame, level, mode, P, S, rays, ray_stride, z, raw, xw, xw_row, xw_col0, src, num_cus(), st)
-                   : m.f32_split(pk, frame, level, mode, P, S, rays, ray_stride, z, raw, xw, xw_row, xw_col0, src, nullptr, num_cus(), st);
-    });
+    e = probed(probe_kind(model, precision, level, mode), P, st, [&] { return m.field[p->split](&L, mode); });
     return e ? hip_fail(who, e) : 0;
 }
 
@@ -654,7 +586,7 @@ static int field_forward_save(const SaveForm &f, int model, const void *packed, 
     if (f.split && !m.deformation_nets)
         return fail(4, "%s: this model has no deformation nets (its saving forward: sahs_model_field_forward_save%s)", who,
                     f.x3 ? "_bits_x3" : (f.bits ? "_bits" : ""));
-    if (!f.split && f.x3 && !m.x3_save)
+    if (!f.split && f.x3 && m.deformation_nets)
         return fail(4, "%s: this model saves through the split chain on this pipe (sahs_model_field_forward_split_save_bits_x3)", who);
     if (f.split && N == 0) return 0;
     REQUIRE(packed && frame && rays && act_out && (!f.bits || bits_out) && (f.split ? xw != nullptr : z && raw), who);
@@ -668,22 +600,13 @@ static int field_forward_save(const SaveForm &f, int model, const void *packed, 
     const long P = N * S;
     REQUIRE(!f.bits || P <= 4000000L, who);      // (at most 4e6 samples per call)
     if (!f.split && f.bits && P == 0) return 0;
-    const float *pk = (const float *)packed;
-    float *base = act_out - act_col0(model, mode) * P;
     hipStream_t st = (hipStream_t)stream;
-    int e;
-    if (f.x3)
-        e = probed(probe_kind(model, SAHS_BF16X3, level, mode), P, st, [&] {
-            if (!f.split) return m.x3_save(pk, frame, level, P, S, rays, ray_stride, z, raw, act_out, bits_out, num_cus(), st);
-            if (mode == 1) return m.deform_x3_save(pk, frame, level, P, S, rays, ray_stride, z, xw, xw_row, xw_col0, base, bits_out, num_cus(), st);
-            return m.radiance_x3_save(pk, frame, level, P, S, rays, ray_stride, raw, xw, xw_row, src, base, bits_out, num_cus(), st);
-        });
-    else if (f.bits)
-        e = m.f32_split_bits(pk, frame, level, mode, P, S, rays, ray_stride, z, raw, xw, xw_row, xw_col0, src, base, bits_out, num_cus(), st);
-    else if (f.split)
-        e = m.f32_split(pk, frame, level, mode, P, S, rays, ray_stride, z, raw, xw, xw_row, xw_col0, src, base, num_cus(), st);
-    else
-        e = m.f32(pk, frame, level, P, S, rays, ray_stride, z, raw, nullptr, act_out, num_cus(), st);
+    // (a whole-network form has mode 0, no xw and no src; column 0 of its part is column 0 of the table: the base is act_out)
+    const FieldLaunch L{.packed = (const float *)packed, .frame = frame, .level = level, .P = P, .S = S, .rays = rays, .ray_stride = ray_stride,
+                        .zvals = z, .raw = raw, .xw = xw, .xw_row = xw_row, .xw_col0 = xw_col0, .src = src,
+                        .actbuf = act_out - act_col0(model, mode) * P, .bits = bits_out, .num_cu = num_cus(), .stream = st};
+    int e = f.x3 ? probed(probe_kind(model, SAHS_BF16X3, level, mode), P, st, [&] { return m.field[K_X3](&L, mode); })
+                 : m.field[K_F32](&L, mode);
     return e ? hip_fail(who, e) : 0;
 }
 
@@ -798,43 +721,6 @@ int sahs_model_field_backward_fused(int model, const float *flat_params, const f
     return e ? hip_fail(who, e) : 0;
 }
 
-int sahs_model_render_rays_rows(int model, const void *packed, const float *frame, int precision, long N, const float *rays,
-                                int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand,
-                                const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f, float *raw,
-                                float *weights, float *rows, int row_ld, float *xw, int32_t *src, float *z_new, void *stream)
-{
-    const char *who = "sahs_model_render_rays_rows";
-    REQUIRE_MODEL(model, who);
-    if (N == 0) return 0;
-    REQUIRE(rows && row_ld >= SAHS_ROW_COLUMNS, who);
-    const Pipe *p = pipe_of(model, precision);
-    const bool deform = kModels[model].deformation_nets;
-    if (deform && p && p->chain != K_NONE)      // a pair that exists only as the split chain needs its workspace
-        REQUIRE(xw && src && z_new && nf > 0, who);
-    if (xw && src && z_new && nf > 0 && deform && p && (p->split != K_NONE || p->chain != K_NONE)) {
-        // the deformation nets are shared by the two levels and the fine depths contain the coarse ones: evaluate them once per depth
-        REQUIRE(packed && frame && rays && z_c && z_f && raw && weights && Sc + nf <= 256, who);
-        const int Sf = Sc + nf;
-        hipStream_t st = (hipStream_t)stream;
-        int e;
-        if ((e = sahs_stratified_depths(N, Sc, rays, ray_stride, lindisp, t_rand, z_c, stream))) return e;
-        if ((e = sahs_model_field_forward_split(model, packed, frame, precision, 0, 0, N, Sc, rays, ray_stride, z_c, raw, xw, Sf, 0, nullptr, stream))) return e;
-        e = sahs_composite_forward_launch(N, Sc, raw, z_c, rays, ray_stride, noise_c, bg, white_background, rows + SAHS_ROW_RGB_C, rows + SAHS_ROW_DISP_C,
-                                          rows + SAHS_ROW_ACC_C, weights, nullptr, nullptr, row_ld, row_ld, st);
-        if (e) return hip_fail(who, e);
-        if ((e = sahs_resample_merge(N, Sc, nf, z_c, weights, u, z_new, z_f, src, stream))) return e;
-        if ((e = sahs_model_field_forward_split(model, packed, frame, precision, 1, 1, N, nf, rays, ray_stride, z_new, nullptr, xw, Sf, Sc, nullptr, stream))) return e;
-        if ((e = sahs_model_field_forward_split(model, packed, frame, precision, 1, 2, N, Sf, rays, ray_stride, nullptr, raw, xw, Sf, 0, src, stream))) return e;
-        e = sahs_composite_forward_launch(N, Sf, raw, z_f, rays, ray_stride, noise_f, bg, white_background, rows + SAHS_ROW_RGB_F, rows + SAHS_ROW_DISP_F,
-                                          rows + SAHS_ROW_ACC_F, weights, rows + SAHS_ROW_DEPTH_F, rows + SAHS_ROW_W_BG, row_ld, row_ld, st);
-        return e ? hip_fail(who, e) : 0;
-    }
-    return render_rays_chain(who, model, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp, white_background, bg, t_rand, noise_c,
-                             u, noise_f, z_c, z_f, raw, weights, rows + SAHS_ROW_RGB_C, rows + SAHS_ROW_DISP_C, rows + SAHS_ROW_ACC_C,
-                             rows + SAHS_ROW_RGB_F, rows + SAHS_ROW_DISP_F, rows + SAHS_ROW_ACC_F, rows + SAHS_ROW_W_BG, rows + SAHS_ROW_DEPTH_F,
-                             stream, row_ld, row_ld);
-}
-
 // ---- sparse branches (fp32 inference render): see csrc/field_f32.hip, FIELD_ALL_FUSED / FIELD_RADIANCE_FUSED ----
 // One radiance evaluation of the render chain: ONE launch over the pass, the workspace holding the workgroups' record rings (never more
 // than the pass's samples rounded up to a tile, at most 512 slots per CU; the caller has checked that they fit), and ONE probe record of
@@ -848,20 +734,132 @@ static long sparse_capacity(int model, size_t ws_bytes)      // record slots (a 
     long cap = ((long)ws_bytes - head) / rec / 128 * 128;
     return cap > (1L << 30) ? (1L << 30) : cap;
 }
-static int field_forward_sparse(const char *who, int model, const float *pk, const float *frame, int level, int stage, int part, long N, int S,
-                                const float *rays, int ray_stride, const float *z, float *raw, float *xw, int xw_row, const int32_t *src,
-                                const float *noise, int has_bg, void *ws, long cap, hipStream_t st)
+static int field_forward_sparse(const char *who, int model, const FieldLaunch &L, int stage, int part, const float *noise, int has_bg, void *ws, long cap)
 {
-    const ModelFns &m = kModels[model];
-    int e = probed(probe_kind(model, SAHS_F32, level, part), N * S, st, [&] {
-        hipError_t he = hipMemsetAsync(ws, 0, 8, st);
+    int e = probed(probe_kind(model, SAHS_F32, L.level, part), L.P, L.stream, [&] {
+        hipError_t he = hipMemsetAsync(ws, 0, 8, L.stream);
         if (he != hipSuccess) return (int)he;
-        return m.f32_sparse(pk, frame, level, stage, N * S, S, rays, ray_stride, z, raw, xw, xw_row, 0, src, noise, has_bg, ws, cap, num_cus(), st);
+        return kModels[model].f32_sparse(&L, stage, noise, has_bg, ws, cap);
     });
     // (negative: the launcher's own refusals, not HIP errors -- unreachable through the caller's checks, named in case a change breaks them)
-    if (e == -4) return fail(5, "%s: the sparse-branch launcher refused its record workspace (%ld slots for the rings of %ld samples)", who, cap, N * S);
+    if (e == -4) return fail(5, "%s: the sparse-branch launcher refused its record workspace (%ld slots for the rings of %ld samples)", who, cap, L.P);
     if (e < 0) return fail(4, "%s: the sparse-branch launcher has no stage %d for this model", who, stage);
     return e ? hip_fail(who, e) : 0;
+}
+
+// ---- the render chain: depths -> field level 0 -> composite -> resample -> field level 1 -> composite, one body for every entry point ----
+// How a level's field pass is evaluated: `shared` (xw, src, z_new given): the deformation nets are shared by the two levels and the fine
+// depths contain the coarse ones, so they run once per depth -- the coarse pass writes x', w to xw, a deformation launch adds the new
+// depths', and the fine pass is the radiance nets on xw through the merge permutation src; otherwise each level is the whole network.
+// `ws` given: the fp32 passes that reach the radiance nets are the sparse-branch launches on that record workspace of `cap` slots.
+// The callers have checked their own arguments; a chain that came here unchecked for its sample counts is refused where it always was,
+// behind the coarse field launch.
+struct RenderWork {
+    float *xw;      // shared evaluation: (N, Sc + nf, 8) x', w; src (N, Sc + nf) and z_new (N, nf) of the merge
+    int32_t *src;
+    float *z_new;
+    void *ws;       // sparse branches: the record workspace and its slots
+    long cap;
+};
+static int render_chain(const char *who, int model, const void *packed, const float *frame, int precision, long N, const float *rays,
+                        int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand,
+                        const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f, float *raw, float *weights,
+                        CompositeOut coarse, const CompositeOut &fine, const RenderWork &w, void *stream)
+{
+    const bool shared = w.xw != nullptr, sparse = w.ws != nullptr;
+    const int Sf = Sc + nf, has_bg = bg != nullptr;
+    const float *pk = (const float *)packed;
+    hipStream_t st = (hipStream_t)stream;
+    // a sparse pass of S samples per ray: stage 0 the whole network on the depths z (x', w to xw_io when given), 1 the radiance nets on w.xw
+    auto sparse_pass = [&](int level, int stage, int S, const float *z, float *xw_io, int xw_row, const int32_t *src_in, const float *noise) {
+        const FieldLaunch L{.packed = pk, .frame = frame, .level = level, .P = N * S, .S = S, .rays = rays, .ray_stride = ray_stride, .zvals = z,
+                            .raw = raw, .xw = xw_io, .xw_row = xw_row, .src = src_in, .num_cu = num_cus(), .stream = st};
+        return field_forward_sparse(who, model, L, stage, stage == 0 ? 0 : 2, noise, has_bg, w.ws, w.cap);
+    };
+    int e;
+    if ((e = sahs_stratified_depths(N, Sc, rays, ray_stride, lindisp, t_rand, z_c, stream))) return e;
+    if (sparse)
+        e = sparse_pass(0, 0, Sc, z_c, w.xw, Sf, nullptr, noise_c);
+    else if (shared)
+        e = sahs_model_field_forward_split(model, packed, frame, precision, 0, 0, N, Sc, rays, ray_stride, z_c, raw, w.xw, Sf, 0, nullptr, stream);
+    else
+        e = field_forward(who, model, packed, frame, 0, N, Sc, rays, ray_stride, z_c, raw, nullptr, precision, stream);
+    if (e) return e;
+    REQUIRE(Sc <= 256, who);
+    if (nf == 0) coarse.depth = fine.depth, coarse.w_last = fine.w_last;      // (the reference returns the last pass's depth only)
+    e = composite_launch(N, Sc, raw, z_c, rays, ray_stride, noise_c, bg, white_background, weights, coarse, st);
+    if (e) return hip_fail(who, e);
+    if (nf == 0) return 0;
+    REQUIRE(Sf <= 256, who);
+    if (shared) {
+        if ((e = sahs_resample_merge(N, Sc, nf, z_c, weights, u, w.z_new, z_f, w.src, stream))) return e;
+        if ((e = sahs_model_field_forward_split(model, packed, frame, precision, 1, 1, N, nf, rays, ray_stride, w.z_new, nullptr, w.xw, Sf, Sc, nullptr, stream))) return e;
+        e = sparse ? sparse_pass(1, 1, Sf, nullptr, w.xw, Sf, w.src, noise_f)
+                   : sahs_model_field_forward_split(model, packed, frame, precision, 1, 2, N, Sf, rays, ray_stride, nullptr, raw, w.xw, Sf, 0, w.src, stream);
+    } else {
+        if ((e = sahs_resample(N, Sc, nf, z_c, weights, u, nullptr, z_f, nullptr, stream))) return e;
+        e = sparse ? sparse_pass(1, 0, Sf, z_f, nullptr, 0, nullptr, noise_f)
+                   : field_forward(who, model, packed, frame, 1, N, Sf, rays, ray_stride, z_f, raw, nullptr, precision, stream);
+    }
+    if (e) return e;
+    e = composite_launch(N, Sf, raw, z_f, rays, ray_stride, noise_f, bg, white_background, weights, fine, st);
+    return e ? hip_fail(who, e) : 0;
+}
+
+// the dense chain, each level the whole network: its own checks, then the body
+static int render_rays_chain(const char *who, int model, const void *packed, const float *frame, int precision, long N,
+                             const float *rays, int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg,
+                             const float *t_rand, const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f,
+                             float *raw, float *weights, const CompositeOut &coarse, const CompositeOut &fine, void *stream)
+{
+    if (N == 0) return 0;   // an empty ray chunk: nothing to launch (its tensors have null data pointers)
+    REQUIRE(packed && frame && rays && z_c && raw && weights && coarse.rgb && coarse.disp && coarse.acc && fine.w_last && fine.depth, who);
+    REQUIRE(nf == 0 || (z_f && fine.rgb && fine.disp && fine.acc), who);
+    return render_chain(who, model, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp, white_background, bg, t_rand, noise_c, u, noise_f,
+                        z_c, z_f, raw, weights, coarse, fine, RenderWork{}, stream);
+}
+
+int sahs_render_rays(const void *packed, const float *frame, int precision, long N, const float *rays, int ray_stride, int Sc, int nf,
+                     int lindisp, int white_background, const float *bg, const float *t_rand, const float *noise_c, const float *u,
+                     const float *noise_f, float *z_c, float *z_f, float *raw, float *weights, float *rgb_c, float *disp_c,
+                     float *acc_c, float *rgb_f, float *disp_f, float *acc_f, float *w_bg, float *depth_f, void *stream)
+{
+    return render_rays_chain("sahs_render_rays", SAHS_MODEL_AUDIO, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp,
+                             white_background, bg, t_rand, noise_c, u, noise_f, z_c, z_f, raw, weights,
+                             composite_tensors(rgb_c, disp_c, acc_c, nullptr, nullptr), composite_tensors(rgb_f, disp_f, acc_f, depth_f, w_bg), stream);
+}
+int sahs_model_render_rays(int model, const void *packed, const float *frame, int precision, long N, const float *rays, int ray_stride,
+                           int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand, const float *noise_c,
+                           const float *u, const float *noise_f, float *z_c, float *z_f, float *raw, float *weights, float *rgb_c,
+                           float *disp_c, float *acc_c, float *rgb_f, float *disp_f, float *acc_f, float *w_bg, float *depth_f, void *stream)
+{
+    REQUIRE_MODEL(model, "sahs_model_render_rays");
+    return render_rays_chain("sahs_model_render_rays", model, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp, white_background,
+                             bg, t_rand, noise_c, u, noise_f, z_c, z_f, raw, weights, composite_tensors(rgb_c, disp_c, acc_c, nullptr, nullptr),
+                             composite_tensors(rgb_f, disp_f, acc_f, depth_f, w_bg), stream);
+}
+
+int sahs_model_render_rays_rows(int model, const void *packed, const float *frame, int precision, long N, const float *rays,
+                                int ray_stride, int Sc, int nf, int lindisp, int white_background, const float *bg, const float *t_rand,
+                                const float *noise_c, const float *u, const float *noise_f, float *z_c, float *z_f, float *raw,
+                                float *weights, float *rows, int row_ld, float *xw, int32_t *src, float *z_new, void *stream)
+{
+    const char *who = "sahs_model_render_rays_rows";
+    REQUIRE_MODEL(model, who);
+    if (N == 0) return 0;
+    REQUIRE(rows && row_ld >= SAHS_ROW_COLUMNS, who);
+    const Pipe *p = pipe_of(model, precision);
+    const bool deform = kModels[model].deformation_nets;
+    const CompositeOut coarse = composite_rows(rows, row_ld, false), fine = composite_rows(rows, row_ld, true);
+    if (deform && p && p->chain != K_NONE)      // a pair that exists only as the split chain needs its workspace
+        REQUIRE(xw && src && z_new && nf > 0, who);
+    if (xw && src && z_new && nf > 0 && deform && p && (p->split != K_NONE || p->chain != K_NONE)) {
+        REQUIRE(packed && frame && rays && z_c && z_f && raw && weights && Sc + nf <= 256, who);
+        return render_chain(who, model, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp, white_background, bg, t_rand, noise_c, u,
+                            noise_f, z_c, z_f, raw, weights, coarse, fine, RenderWork{xw, src, z_new, nullptr, 0}, stream);
+    }
+    return render_rays_chain(who, model, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp, white_background, bg, t_rand, noise_c,
+                             u, noise_f, z_c, z_f, raw, weights, coarse, fine, stream);
 }
 
 size_t sahs_model_render_sparse_fused_workspace_bytes(int model, long samples)
@@ -904,31 +902,9 @@ int sahs_model_render_rays_rows_sparse(int model, const void *packed, const floa
         return fail(5, "%s: a sparse-branch workspace of %zu bytes holds %ld record slots, the rings of this render need %ld "
                        "(sahs_model_render_sparse_fused_workspace_bytes)", who, ws_bytes, cap, need);
     const bool shared = xw && src && z_new && nf > 0 && kModels[model].deformation_nets;
-    const float *pk = (const float *)packed;
-    const int Sf = Sc + nf, has_bg = bg != nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    int e;
-    if ((e = sahs_stratified_depths(N, Sc, rays, ray_stride, lindisp, t_rand, z_c, stream))) return e;
-    if ((e = field_forward_sparse(who, model, pk, frame, 0, 0, 0, N, Sc, rays, ray_stride, z_c, raw, shared ? xw : nullptr, Sf, nullptr, noise_c, has_bg, ws,
-                                  cap, st)))
-        return e;
-    // (as in the dense chains: the coarse depth and last weight are written only when there is no fine pass)
-    e = sahs_composite_forward_launch(N, Sc, raw, z_c, rays, ray_stride, noise_c, bg, white_background, rows + SAHS_ROW_RGB_C, rows + SAHS_ROW_DISP_C,
-                                      rows + SAHS_ROW_ACC_C, weights, nf == 0 ? rows + SAHS_ROW_DEPTH_F : nullptr, nf == 0 ? rows + SAHS_ROW_W_BG : nullptr,
-                                      row_ld, row_ld, st);
-    if (e) return hip_fail(who, e);
-    if (nf == 0) return 0;
-    if (shared) {      // the deformation nets once per depth (sahs_model_render_rays_rows), the fine pass's radiance nets with sparse branches
-        if ((e = sahs_resample_merge(N, Sc, nf, z_c, weights, u, z_new, z_f, src, stream))) return e;
-        if ((e = sahs_model_field_forward_split(model, packed, frame, precision, 1, 1, N, nf, rays, ray_stride, z_new, nullptr, xw, Sf, Sc, nullptr, stream))) return e;
-        if ((e = field_forward_sparse(who, model, pk, frame, 1, 1, 2, N, Sf, rays, ray_stride, nullptr, raw, xw, Sf, src, noise_f, has_bg, ws, cap, st))) return e;
-    } else {
-        if ((e = sahs_resample(N, Sc, nf, z_c, weights, u, nullptr, z_f, nullptr, stream))) return e;
-        if ((e = field_forward_sparse(who, model, pk, frame, 1, 0, 0, N, Sf, rays, ray_stride, z_f, raw, nullptr, 0, nullptr, noise_f, has_bg, ws, cap, st))) return e;
-    }
-    e = sahs_composite_forward_launch(N, Sf, raw, z_f, rays, ray_stride, noise_f, bg, white_background, rows + SAHS_ROW_RGB_F, rows + SAHS_ROW_DISP_F,
-                                      rows + SAHS_ROW_ACC_F, weights, rows + SAHS_ROW_DEPTH_F, rows + SAHS_ROW_W_BG, row_ld, row_ld, st);
-    return e ? hip_fail(who, e) : 0;
+    return render_chain(who, model, packed, frame, precision, N, rays, ray_stride, Sc, nf, lindisp, white_background, bg, t_rand, noise_c, u, noise_f,
+                        z_c, z_f, raw, weights, composite_rows(rows, row_ld, false), composite_rows(rows, row_ld, true),
+                        shared ? RenderWork{xw, src, z_new, ws, cap} : RenderWork{nullptr, nullptr, nullptr, ws, cap}, stream);
 }
 
 }  // extern "C"

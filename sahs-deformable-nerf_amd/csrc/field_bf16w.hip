@@ -697,58 +697,38 @@ extern "C" int SAHS_SYM(sahs_bf16w_exact_leaky_state)(int set)
     return cur;
 }
 
+// One launch on a block normalised for its mode (sahs_launchers.hpp: sahs_field_mode_block); the exact-LeakyReLU state is read here, at
+// launch time.
 template <int MODE, bool EXACT>
-static int launch_w2(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, const float *zvals,
-                     float *raw, float *dbg, float *xw, int xw_row, int xw_col0, const int *src, int num_cu, hipStream_t stream)
+static int launch_w2(const FieldLaunch &L)
 {
-    if (P <= 0) return 0;
-    const long ntiles = (P + W_PTS_PER_WG - 1) / W_PTS_PER_WG;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    static sahs_once::Flags attr_set;       // the large-LDS attribute is per device (and per kernel instance)
-    hipError_t ae = sahs_once::per_device(attr_set, [&]() {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(field_forward_bf16w_kernel<MODE, EXACT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    });
-    if (ae != hipSuccess) return (int)ae;
-    field_forward_bf16w_kernel<MODE, EXACT><<<grid, W_THREADS, LDS_BYTES, stream>>>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, dbg, xw, xw_row,
-                                                                                   xw_col0, src);
-    return (int)hipGetLastError();
+    return sahs_launch_persistent<field_forward_bf16w_kernel<MODE, EXACT>>((L.P + W_PTS_PER_WG - 1) / W_PTS_PER_WG, L.num_cu, W_THREADS, LDS_BYTES, L.stream,
+                                                                           L.packed, L.frame, L.level, L.P, L.S, L.rays, L.ray_stride, L.zvals, L.raw, L.dbg,
+                                                                           L.xw, L.xw_row, L.xw_col0, L.src);
 }
 template <int MODE>
-static int launch_w(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, const float *zvals,
-                    float *raw, float *dbg, float *xw, int xw_row, int xw_col0, const int *src, int num_cu, hipStream_t stream)
+static int launch_w(const FieldLaunch &L)
 {
-    return SAHS_SYM(sahs_bf16w_exact_leaky_state)(-1)
-               ? launch_w2<MODE, true>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, dbg, xw, xw_row, xw_col0, src, num_cu, stream)
-               : launch_w2<MODE, false>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, dbg, xw, xw_row, xw_col0, src, num_cu, stream);
+    return SAHS_SYM(sahs_bf16w_exact_leaky_state)(-1) ? launch_w2<MODE, true>(L) : launch_w2<MODE, false>(L);
 }
 
-#if SAHS_MODEL != 1      // whole-network launches: AudioFaceModel, and NeRFaceModel without deformation nets (all of it is the radiance net)
-extern "C" int SAHS_SYM(sahs_field_forward_bf16w_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                                         int ray_stride, const float *zvals, float *raw, float *dbg, int num_cu,
-                                                         hipStream_t stream)
+// The whole network (AudioFaceModel, and NeRFaceModel without deformation nets: all of it is the radiance net) and the split evaluation
+// (field_f32.hip: sahs_field_f32_launch, same block; nothing is saved).  NeRFaceModel has the radiance nets only (mode 2; src may be null =
+// sample s of a ray is column s of xw): that model's deformation nets stay fp32.
+extern "C" int SAHS_SYM(sahs_field_bf16w_launch)(const FieldLaunch *in, int mode)
 {
-    return launch_w<FIELD_ALL>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, dbg, nullptr, 0, 0, nullptr, num_cu, stream);
-}
-#endif
-
-#if SAHS_MODEL != 2
-// the split evaluation (field_f32.hip: sahs_field_forward_f32_split_launch, same arguments).  Built for NeRFaceModel too, radiance nets
-// only (mode 2; src may be null = sample s of a ray is column s of xw): that model's deformation nets stay fp32.
-extern "C" int SAHS_SYM(sahs_field_forward_bf16w_split_launch)(const float *packed, const float *frame, int level, int mode, long P, int S,
-                                                               const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,
-                                                               int xw_row, int xw_col0, const int *src, int num_cu, hipStream_t stream)
-{
+    if (in->P <= 0) return 0;
+    const FieldLaunch L = sahs_field_mode_block(*in, mode);
     switch (mode) {
-#if SAHS_MODEL == 0
-    case FIELD_ALL:
-        return launch_w<FIELD_ALL>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream);
-    case FIELD_DEFORM:
-        return launch_w<FIELD_DEFORM>(packed, frame, level, P, S, rays, ray_stride, zvals, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream);
+#if SAHS_MODEL != 1
+    case FIELD_ALL: return launch_w<FIELD_ALL>(L);
 #endif
-    case FIELD_RADIANCE:
-        return launch_w<FIELD_RADIANCE>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, xw, xw_row, 0, src, num_cu, stream);
-    default:
-        return -2;
+#if SAHS_MODEL == 0
+    case FIELD_DEFORM: return launch_w<FIELD_DEFORM>(L);
+#endif
+#if SAHS_MODEL != 2
+    case FIELD_RADIANCE: return launch_w<FIELD_RADIANCE>(L);
+#endif
+    default: return -2;
     }
 }
-#endif

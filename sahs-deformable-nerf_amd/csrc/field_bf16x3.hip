@@ -461,85 +461,43 @@ field_deform_bf16x3_kernel(const float *__restrict__ packed, const float *__rest
 using namespace SAHS_NS;
 using namespace SAHS_NS::hx3;
 
+// One launch on a block normalised for its mode (sahs_launchers.hpp: sahs_field_mode_block), saving when SAVE.
 template <bool SAVE>
-static int launch_radiance_x3(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, const float *zvals,
-                              float *raw, const float *xw, int xw_row, const int *src, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream)
+static int launch_radiance_x3(const FieldLaunch &L)
 {
-    if (P <= 0) return 0;
-    if (SAVE && P * (long)(4 * 256) >= (1L << 32)) return -4;      // (SaveAct: 32-bit byte offsets inside a layer's plane)
-    const long ntiles = (P + X_PTS_PER_WG - 1) / X_PTS_PER_WG;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    static sahs_once::Flags attr_set;
-    hipError_t ae = sahs_once::per_device(attr_set, [&]() {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(field_radiance_bf16x3_kernel<SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, SAVE ? LDS_BYTES_SAVE : LDS_BYTES);
-    });
-    if (ae != hipSuccess) return (int)ae;
-    field_radiance_bf16x3_kernel<SAVE><<<grid, X_THREADS, SAVE ? LDS_BYTES_SAVE : LDS_BYTES, stream>>>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, xw,
-                                                                                                      xw_row, src, actbuf, bits);
-    return (int)hipGetLastError();
+    if (SAVE && L.P * (long)(4 * 256) >= (1L << 32)) return -4;      // (SaveAct: 32-bit byte offsets inside a layer's plane)
+    return sahs_launch_persistent<field_radiance_bf16x3_kernel<SAVE>>((L.P + X_PTS_PER_WG - 1) / X_PTS_PER_WG, L.num_cu, X_THREADS, SAVE ? LDS_BYTES_SAVE : LDS_BYTES,
+                                                                      L.stream, L.packed, L.frame, L.level, L.P, L.S, L.rays, L.ray_stride, L.zvals, L.raw, L.xw,
+                                                                      L.xw_row, L.src, L.actbuf, L.bits);
 }
 #if SAHS_MODEL != 2
-// the radiance launch of the split evaluation (field_f32.hip: sahs_field_forward_f32_split_launch mode 2, same arguments)
-extern "C" int SAHS_SYM(sahs_field_radiance_bf16x3_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                                           int ray_stride, float *raw, const float *xw, int xw_row, const int *src, int num_cu,
-                                                           hipStream_t stream)
+template <bool SAVE>
+static int launch_deform_x3(const FieldLaunch &L)
 {
-    return launch_radiance_x3<false>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, xw, xw_row, src, nullptr, nullptr, num_cu, stream);
-}
-// ... that also saves what the backward reads (field_f32.hip: sahs_field_forward_f32_split_bits_launch mode 2 with actbuf and bits, same buffers)
-extern "C" int SAHS_SYM(sahs_field_radiance_bf16x3_save_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                                                int ray_stride, float *raw, const float *xw, int xw_row, const int *src, float *actbuf,
-                                                                uint32_t *bits, int num_cu, hipStream_t stream)
-{
-    if (actbuf == nullptr || bits == nullptr) return -2;
-    return launch_radiance_x3<true>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, xw, xw_row, src, actbuf, bits, num_cu, stream);
-}
-#else
-// model 2: the whole network on the depths zvals (field_f32.hip: sahs_field_forward_f32_launch without dbg / actbuf, same arguments)
-extern "C" int SAHS_SYM(sahs_field_forward_bf16x3_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                                          int ray_stride, const float *zvals, float *raw, int num_cu, hipStream_t stream)
-{
-    return launch_radiance_x3<false>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, 0, nullptr, nullptr, nullptr, num_cu, stream);
-}
-// ... that also saves what the backward reads (field_f32.hip: sahs_field_forward_f32_split_bits_launch mode 0 with actbuf and bits, same buffers)
-extern "C" int SAHS_SYM(sahs_field_forward_bf16x3_save_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                                               int ray_stride, const float *zvals, float *raw, float *actbuf, uint32_t *bits, int num_cu,
-                                                               hipStream_t stream)
-{
-    if (actbuf == nullptr || bits == nullptr) return -2;
-    return launch_radiance_x3<true>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, 0, nullptr, actbuf, bits, num_cu, stream);
+    if (SAVE && L.P * (long)(4 * 128) >= (1L << 32)) return -4;
+    return sahs_launch_persistent<field_deform_bf16x3_kernel<SAVE>>((L.P + X_PTS_PER_WG - 1) / X_PTS_PER_WG, L.num_cu, X_THREADS, SAVE ? LDS_BYTES_SAVE : LDS_BYTES,
+                                                                    L.stream, L.packed, L.frame, L.level, L.P, L.S, L.rays, L.ray_stride, L.zvals, L.xw, L.xw_row,
+                                                                    L.xw_col0, L.actbuf, L.bits);
 }
 #endif
 
-#if SAHS_MODEL != 2
-template <bool SAVE>
-static int launch_deform_x3(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, const float *zvals,
-                            float *xw, int xw_row, int xw_col0, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream)
+// The split-operand kernels on the block of field_f32.hip's sahs_field_f32_launch (no debug planes).  With deformation nets: mode 1 the
+// deformation launch, mode 2 the radiance launch of the split evaluation; without (model 2): mode 0, the whole network on the depths zvals.
+// actbuf and bits together: the launch also saves what the backward reads (the buffers of the fp32 launch of that mode that saves with
+// sign bits); one of them alone is refused.
+extern "C" int SAHS_SYM(sahs_field_bf16x3_launch)(const FieldLaunch *in, int mode)
 {
-    if (P <= 0) return 0;
-    if (SAVE && P * (long)(4 * 128) >= (1L << 32)) return -4;
-    const long ntiles = (P + X_PTS_PER_WG - 1) / X_PTS_PER_WG;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    static sahs_once::Flags attr_set;
-    hipError_t ae = sahs_once::per_device(attr_set, [&]() {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(field_deform_bf16x3_kernel<SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, SAVE ? LDS_BYTES_SAVE : LDS_BYTES);
-    });
-    if (ae != hipSuccess) return (int)ae;
-    field_deform_bf16x3_kernel<SAVE><<<grid, X_THREADS, SAVE ? LDS_BYTES_SAVE : LDS_BYTES, stream>>>(packed, frame, level, P, S, rays, ray_stride, zvals, xw, xw_row, xw_col0, actbuf, bits);
-    return (int)hipGetLastError();
+    if (in->P <= 0) return 0;
+    const bool save = in->actbuf != nullptr || in->bits != nullptr;
+    if (save && (in->actbuf == nullptr || in->bits == nullptr)) return -2;
+    const FieldLaunch L = sahs_field_mode_block(*in, mode);
+    switch (mode) {
+#if SAHS_MODEL == 2
+    case 0: return save ? launch_radiance_x3<true>(L) : launch_radiance_x3<false>(L);
+#else
+    case 1: return save ? launch_deform_x3<true>(L) : launch_deform_x3<false>(L);
+    case 2: return save ? launch_radiance_x3<true>(L) : launch_radiance_x3<false>(L);
+#endif
+    default: return -2;
+    }
 }
-// the deformation launch of the split evaluation (field_f32.hip: sahs_field_forward_f32_split_launch mode 1, same arguments)
-extern "C" int SAHS_SYM(sahs_field_deform_bf16x3_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride,
-                                               const float *zvals, float *xw, int xw_row, int xw_col0, int num_cu, hipStream_t stream)
-{
-    return launch_deform_x3<false>(packed, frame, level, P, S, rays, ray_stride, zvals, xw, xw_row, xw_col0, nullptr, nullptr, num_cu, stream);
-}
-// ... that also saves what the backward reads (field_f32.hip: sahs_field_forward_f32_split_bits_launch mode 1 with actbuf and bits, same buffers)
-extern "C" int SAHS_SYM(sahs_field_deform_bf16x3_save_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                                              int ray_stride, const float *zvals, float *xw, int xw_row, int xw_col0, float *actbuf,
-                                                              uint32_t *bits, int num_cu, hipStream_t stream)
-{
-    if (actbuf == nullptr || bits == nullptr) return -2;
-    return launch_deform_x3<true>(packed, frame, level, P, S, rays, ray_stride, zvals, xw, xw_row, xw_col0, actbuf, bits, num_cu, stream);
-}
-#endif      // SAHS_MODEL != 2

@@ -530,25 +530,17 @@ extern "C" int SAHS_SYM(sahs_bwd_chain_pack_launch)(const float *flat, void *str
     return (int)hipGetLastError();
 }
 
-template <class K, class... A>
-static int launch_chain(K kernel, long P, int num_cu, hipStream_t stream, A... args)
+template <auto Kernel, class... A>
+static int launch_chain(long P, int num_cu, hipStream_t stream, A... args)
 {
     if (P <= 0) return 0;
-    const long ntiles = (P + X_PTS_PER_WG - 1) / X_PTS_PER_WG;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    static sahs_once::Flags attr_set;       // (one per instantiation = per kernel)
-    hipError_t ae = sahs_once::per_device(attr_set, [&]() {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BWC_LDS_BYTES);
-    });
-    if (ae != hipSuccess) return (int)ae;
-    kernel<<<grid, X_THREADS, BWC_LDS_BYTES, stream>>>(args...);
-    return (int)hipGetLastError();
+    return sahs_launch_persistent<Kernel>((P + X_PTS_PER_WG - 1) / X_PTS_PER_WG, num_cu, X_THREADS, BWC_LDS_BYTES, stream, args...);
 }
 
 extern "C" int SAHS_SYM(sahs_bwd_chain_rad_launch)(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf,
                                          float *din_a, float *din_b, int num_cu, hipStream_t stream)
 {
-    return launch_chain(field_backward_chain_rad_kernel, P, num_cu, stream, reinterpret_cast<const unsigned short *>(bstream), P, d_raw, bits, dact,
+    return launch_chain<field_backward_chain_rad_kernel>(P, num_cu, stream, reinterpret_cast<const unsigned short *>(bstream), P, d_raw, bits, dact,
                         dgridf, din_a, din_b);
 }
 
@@ -556,7 +548,7 @@ extern "C" int SAHS_SYM(sahs_bwd_chain_rad_launch)(const void *bstream, long P, 
 extern "C" int SAHS_SYM(sahs_bwd_chain_def_launch)(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact,
                                          float *g3, float *dw4, int num_cu, hipStream_t stream)
 {
-    return launch_chain(field_backward_chain_def_kernel, P, num_cu, stream, reinterpret_cast<const unsigned short *>(bstream), P, xwg, actbuf, bits,
+    return launch_chain<field_backward_chain_def_kernel>(P, num_cu, stream, reinterpret_cast<const unsigned short *>(bstream), P, xwg, actbuf, bits,
                         dact, g3, dw4);
 }
 #endif

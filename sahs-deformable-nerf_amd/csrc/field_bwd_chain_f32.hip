@@ -390,32 +390,23 @@ extern "C" int SAHS_SYM(sahs_bwd_chain_f32_pack_launch)(const float *flat, float
     return (int)hipGetLastError();
 }
 
-template <class K, class... A>
-static int launch_chain_f32(K kernel, long P, int num_cu, hipStream_t stream, A... args)
+template <auto Kernel, class... A>
+static int launch_chain_f32(long P, int num_cu, hipStream_t stream, A... args)
 {
     if (P <= 0) return 0;
-    const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
-    constexpr int LDS_BYTES = CHAIN_LDS_BYTES;
-    static sahs_once::Flags attr_set;       // (one per instantiation = per kernel)
-    hipError_t ae = sahs_once::per_device(attr_set, [&]() {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    });
-    if (ae != hipSuccess) return (int)ae;
-    kernel<<<grid, F32_THREADS, LDS_BYTES, stream>>>(args...);
-    return (int)hipGetLastError();
+    return sahs_launch_persistent<Kernel>((P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG, num_cu, F32_THREADS, CHAIN_LDS_BYTES, stream, args...);
 }
 
 extern "C" int SAHS_SYM(sahs_bwd_chain_f32_rad_launch)(const float *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact, float *dgridf,
                                              float *din_a, float *din_b, int num_cu, hipStream_t stream)
 {
-    return launch_chain_f32(field_backward_chain_rad_f32_kernel, P, num_cu, stream, bstream, P, d_raw, bits, dact, dgridf, din_a, din_b);
+    return launch_chain_f32<field_backward_chain_rad_f32_kernel>(P, num_cu, stream, bstream, P, d_raw, bits, dact, dgridf, din_a, din_b);
 }
 
 #if SAHS_MODEL != 2
 extern "C" int SAHS_SYM(sahs_bwd_chain_f32_def_launch)(const float *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits, float *dact,
                                              float *g3, float *dw4, int num_cu, hipStream_t stream)
 {
-    return launch_chain_f32(field_backward_chain_def_f32_kernel, P, num_cu, stream, bstream, P, xwg, actbuf, bits, dact, g3, dw4);
+    return launch_chain_f32<field_backward_chain_def_f32_kernel>(P, num_cu, stream, bstream, P, xwg, actbuf, bits, dact, g3, dw4);
 }
 #endif

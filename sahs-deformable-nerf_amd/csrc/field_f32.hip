@@ -639,82 +639,45 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
 
 using namespace SAHS_NS;
 
+// One launch of the field kernel on a block normalised for its mode (sahs_launchers.hpp: sahs_field_mode_block).
 // dbg (optional, may be null): [P x 24: see DBG_STRIDE][P x 32: grid features]
 template <bool SAVE, int MODE>
-static int launch_field(const float *packed, const float *frame, int level, long P, int S, const float *rays, int ray_stride, const float *zvals,
-                        float *raw, float *dbg, float *actbuf, float *xw, int xw_row, int xw_col0, const int *src, int num_cu, hipStream_t stream,
-                        uint32_t *bits = nullptr, SparseArgs sp = SparseArgs{})
+static int launch_field(const FieldLaunch &L, SparseArgs sp = SparseArgs{})
 {
-    const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG;
-    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
     const size_t lds_bytes = (size_t)(LDS_TOTAL_FLOATS + ((MODE == FIELD_ALL_FUSED || MODE == FIELD_RADIANCE_FUSED) ? LDS_RING_FLOATS : 0)) * sizeof(float);
-    static sahs_once::Flags attr_set;       // the large-LDS attribute is per device (and per instantiation)
-    hipError_t ae = sahs_once::per_device(attr_set, [&]() {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(field_forward_f32_kernel<SAVE, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds_bytes);
-    });
-    if (ae != hipSuccess) return (int)ae;
-    field_forward_f32_kernel<SAVE, MODE><<<grid, F32_THREADS, lds_bytes, stream>>>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, dbg, actbuf,
-                                                                                   xw, xw_row, xw_col0, src, bits, sp);
-    return (int)hipGetLastError();
+    return sahs_launch_persistent<field_forward_f32_kernel<SAVE, MODE>>((L.P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG, L.num_cu, F32_THREADS, lds_bytes, L.stream,
+                                                                        L.packed, L.frame, L.level, L.P, L.S, L.rays, L.ray_stride, L.zvals, L.raw, L.dbg,
+                                                                        L.actbuf, L.xw, L.xw_row, L.xw_col0, L.src, L.bits, sp);
 }
 
-extern "C" int SAHS_SYM(sahs_field_forward_f32_launch)(const float *packed, const float *frame, int level, long P, int S, const float *rays,
-                                             int ray_stride, const float *zvals, float *raw, float *dbg, float *actbuf, int num_cu,
-                                             hipStream_t stream)
+// The whole network and its split evaluation (see the kernel's MODE, and FieldLaunch for what each mode reads).  actbuf: a saved array of
+// act:: column c starts at actbuf + c * P as for whole-network launches, so a radiance-only launch touches columns >= act::XW only and a
+// deformation-only launch columns < act::XW + 16: the caller may pass a base such that only that range is backed by memory
+// (sahs_layout_act_part_words).  bits (with actbuf): the sign-bit planes of the layers the launch runs (sahs_layout.hpp: sbits; mode 0:
+// [deformation | radiance] planes), (P * sahs_layout_bits_part_words(mode)) 32-bit words, or null.
+extern "C" int SAHS_SYM(sahs_field_f32_launch)(const FieldLaunch *in, int mode)
 {
-    if (P <= 0) return 0;
-    if (actbuf != nullptr)
-        return launch_field<true, FIELD_ALL>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, dbg, actbuf, nullptr, 0, 0, nullptr, num_cu, stream);
-    return launch_field<false, FIELD_ALL>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, dbg, nullptr, nullptr, 0, 0, nullptr, num_cu, stream);
-}
-
-// The split evaluation (see the kernel's MODE): mode 0 = whole network, additionally writing x', w of every sample to xw; mode 1 =
-// deformation nets only (raw unused); mode 2 = radiance net only on x', w fetched through src (zvals unused).
-// actbuf != nullptr: also save the activations of the layers the launch runs (training).  A saved array of act:: column c starts at
-// actbuf + c * P as for whole-network launches, so a radiance-only launch touches columns >= act::XW only and a deformation-only launch
-// columns < act::XW + 16: the caller may pass a base such that only that range is backed by memory (sahs_layout_act_part_words).
-// bits (with actbuf): the sign-bit planes of the layers the launch runs (sahs_layout.hpp: sbits; mode 0: [deformation | radiance] planes),
-// (P * sahs_layout_bits_part_words(mode)) 32-bit words, or null
-extern "C" int SAHS_SYM(sahs_field_forward_f32_split_launch)(const float *packed, const float *frame, int level, int mode, long P, int S,
-                                                   const float *rays, int ray_stride, const float *zvals, float *raw, float *xw, int xw_row,
-                                                   int xw_col0, const int *src, float *actbuf, int num_cu, hipStream_t stream)
-{
-    return SAHS_SYM(sahs_field_forward_f32_split_bits_launch)(packed, frame, level, mode, P, S, rays, ray_stride, zvals, raw, xw, xw_row, xw_col0, src, actbuf,
-                                                              nullptr, num_cu, stream);
-}
-extern "C" int SAHS_SYM(sahs_field_forward_f32_split_bits_launch)(const float *packed, const float *frame, int level, int mode, long P, int S,
-                                                   const float *rays, int ray_stride, const float *zvals, float *raw, float *xw, int xw_row,
-                                                   int xw_col0, const int *src, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream)
-{
-    if (P <= 0) return 0;
+    if (in->P <= 0) return 0;
+    FieldLaunch L = sahs_field_mode_block(*in, mode);
+    const bool save = L.actbuf != nullptr;
+    if (!save) L.bits = nullptr;
 #if SAHS_MODEL == 2
-    // no deformation nets in this model: the whole network only -- with saved activations, the training forward that writes its sign bits
-    // (capi: sahs_model_field_forward_save_bits)
-    if (mode != FIELD_ALL || actbuf == nullptr) return -3;
-    return launch_field<true, FIELD_ALL>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, actbuf, xw, xw_row, xw_col0, nullptr, num_cu, stream, bits);
-#else
-    if (actbuf != nullptr) {
-        if (mode == FIELD_ALL)
-            return launch_field<true, FIELD_ALL>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, actbuf, xw, xw_row, xw_col0, nullptr, num_cu, stream, bits);
-        if (mode == FIELD_DEFORM)
-            return launch_field<true, FIELD_DEFORM>(packed, frame, level, P, S, rays, ray_stride, zvals, nullptr, nullptr, actbuf, xw, xw_row, xw_col0, nullptr, num_cu, stream, bits);
-        if (mode == FIELD_RADIANCE)
-            return launch_field<true, FIELD_RADIANCE>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, actbuf, xw, xw_row, 0, src, num_cu, stream, bits);
-        return -2;
-    }
-    if (mode == FIELD_ALL)
-        return launch_field<false, FIELD_ALL>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream);
-    if (mode == FIELD_DEFORM)
-        return launch_field<false, FIELD_DEFORM>(packed, frame, level, P, S, rays, ray_stride, zvals, nullptr, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream);
-    if (mode == FIELD_RADIANCE)
-        return launch_field<false, FIELD_RADIANCE>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, xw, xw_row, 0, src, num_cu, stream);
-    return -2;
+    // no deformation nets in this model: the whole network only, and no x', w written unless it saves (the training forward that writes
+    // its sign bits; capi: sahs_model_field_forward_save_bits)
+    if (mode != FIELD_ALL || (!save && L.xw != nullptr)) return -3;
 #endif
+    switch (mode) {
+    case FIELD_ALL: return save ? launch_field<true, FIELD_ALL>(L) : launch_field<false, FIELD_ALL>(L);
+#if SAHS_MODEL != 2
+    case FIELD_DEFORM: return save ? launch_field<true, FIELD_DEFORM>(L) : launch_field<false, FIELD_DEFORM>(L);
+    case FIELD_RADIANCE: return save ? launch_field<true, FIELD_RADIANCE>(L) : launch_field<false, FIELD_RADIANCE>(L);
+#endif
+    default: return -2;
+    }
 }
 
-// The sparse branches (see the kernel's MODE), one launch for the whole pass.  stage 0: FIELD_ALL_FUSED over (rays, zvals), x', w also
-// written to xw when given; stage 1: FIELD_RADIANCE_FUSED on x', w fetched from xw through src.
+// The sparse branches (see the kernel's MODE), one launch for the whole pass.  stage 0: FIELD_ALL_FUSED, the block read as mode 0 (x', w
+// also written to xw when given); stage 1: FIELD_RADIANCE_FUSED, the block read as mode 2.  Nothing is saved and no debug planes written.
 // ws: sahs_field_f32_sparse_ws_bytes(cap) bytes, 16-byte aligned: [head: two words, zeroed by the caller | headers | feat groups]; cap:
 // record slots, a multiple of 128 and at least the workgroups' rings, sahs_field_f32_sparse_ring_slots(P, num_cu) (never more than P
 // rounded up to 128).  noise / has_bg: the composite's noise of these samples (or null) and whether it is given a background prior --
@@ -726,22 +689,20 @@ extern "C" long SAHS_SYM(sahs_field_f32_sparse_ring_slots)(long P, int num_cu)
     const long ntiles = (P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG, grid = ntiles < num_cu ? ntiles : num_cu;
     return sparse_ring_base(ntiles, grid, grid);
 }
-extern "C" int SAHS_SYM(sahs_field_forward_f32_sparse_launch)(const float *packed, const float *frame, int level, int stage, long P, int S,
-                                                    const float *rays, int ray_stride, const float *zvals, float *raw, float *xw, int xw_row,
-                                                    int xw_col0, const int *src, const float *noise, int has_bg, void *ws, long cap, int num_cu,
-                                                    hipStream_t stream)
+extern "C" int SAHS_SYM(sahs_field_f32_sparse_launch)(const FieldLaunch *in, int stage, const float *noise, int has_bg, void *ws, long cap)
 {
-    if (P <= 0) return 0;
+    if (in->P <= 0) return 0;
     if (ws == nullptr || cap % F32_PTS_PER_WG != 0 || cap > (1L << 30)) return -4;
-    if (cap < SAHS_SYM(sahs_field_f32_sparse_ring_slots)(P, num_cu)) return -4;
+    if (cap < SAHS_SYM(sahs_field_f32_sparse_ring_slots)(in->P, in->num_cu)) return -4;
     char *base = static_cast<char *>(ws);
     SparseArgs sp{noise, reinterpret_cast<unsigned int *>(base), reinterpret_cast<f32x4 *>(base + SPARSE_HEAD_BYTES),
                   reinterpret_cast<f32x4 *>(base + SPARSE_HEAD_BYTES + cap * 16), (unsigned int)cap, has_bg};
-    if (stage == 0)
-        return launch_field<false, FIELD_ALL_FUSED>(packed, frame, level, P, S, rays, ray_stride, zvals, raw, nullptr, nullptr, xw, xw_row, xw_col0, nullptr, num_cu, stream, nullptr, sp);
+    FieldLaunch L = sahs_field_mode_block(*in, stage == 0 ? FIELD_ALL : FIELD_RADIANCE);
+    L.dbg = L.actbuf = nullptr;
+    L.bits = nullptr;
+    if (stage == 0) return launch_field<false, FIELD_ALL_FUSED>(L, sp);
 #if SAHS_MODEL != 2
-    if (stage == 1)
-        return launch_field<false, FIELD_RADIANCE_FUSED>(packed, frame, level, P, S, rays, ray_stride, nullptr, raw, nullptr, nullptr, xw, xw_row, 0, src, num_cu, stream, nullptr, sp);
+    if (stage == 1) return launch_field<false, FIELD_RADIANCE_FUSED>(L, sp);
 #endif
     return -2;
 }

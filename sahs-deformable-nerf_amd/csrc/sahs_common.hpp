@@ -25,6 +25,22 @@ inline hipError_t per_device(Flags &flags, F &&action)
 }
 }  // namespace sahs_once
 
+// One launch of a persistent kernel: a workgroup per tile, at most one per CU (the kernel walks the tiles), with lds_bytes of dynamic LDS
+// -- more than a kernel gets by default, so the attribute that allows it is set first, once per device and kernel (the flags are this
+// instantiation's own).  Returns the HIP error of the attribute or of the launch, 0 for none.
+template <auto Kernel, class... A>
+inline int sahs_launch_persistent(long ntiles, int num_cu, int threads, size_t lds_bytes, hipStream_t stream, A... args)
+{
+    const int grid = (int)(ntiles < num_cu ? ntiles : num_cu);
+    static sahs_once::Flags attr_set;
+    hipError_t ae = sahs_once::per_device(attr_set, [&]() {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    });
+    if (ae != hipSuccess) return (int)ae;
+    Kernel<<<grid, threads, lds_bytes, stream>>>(args...);
+    return (int)hipGetLastError();
+}
+
 // Timing-only switches and tuning aids are read from the environment by SAHS_DIAG builds only (tools/ablate.py); the shipped library,
 // which build.py refuses to build with extra defines, takes the default of each: there this is a constant null.
 #ifdef SAHS_DIAG

@@ -5,6 +5,42 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+// The facts of one field-forward launch, the same block for every kernel family (fp32, bf16, split-operand).  A launcher takes it with a
+// mode: 0 the whole network, 1 the deformation nets only, 2 the radiance nets only.  What a mode reads:
+//   every mode   packed, frame, level, P (samples), S (samples per ray), rays, ray_stride, num_cu, stream
+//   zvals        modes 0, 1: the depths, P floats
+//   raw          modes 0, 2: the network's output rows
+//   xw           mode 0 (optional): x', w of sample s of a ray written to column xw_col0 + s of the ray's row of xw_row columns;
+//                mode 1: the same, required; mode 2: read, column src[ray][s] (src null: column s); xw_col0 is not used
+//   dbg          mode 0 without xw only (optional): the debug planes of the kernels that have them
+//   actbuf       optional: also save the activations of the layers the launch runs (training); bits: with actbuf, their sign-bit planes
+struct FieldLaunch {
+    const float *packed, *frame;
+    int level;
+    long P;
+    int S;
+    const float *rays;
+    int ray_stride;
+    const float *zvals;
+    float *raw, *dbg;
+    float *xw;
+    int xw_row, xw_col0;
+    const int *src;
+    float *actbuf;
+    uint32_t *bits;
+    int num_cu;
+    hipStream_t stream;
+};
+// ... and the one place where a block is cut down to what its mode reads: the kernels get null (or 0) for everything else
+inline FieldLaunch sahs_field_mode_block(FieldLaunch L, int mode)
+{
+    if (mode == 1) L.raw = nullptr;
+    if (mode == 2) L.zvals = nullptr, L.xw_col0 = 0;
+    else L.src = nullptr;
+    if (mode != 0 || L.xw != nullptr) L.dbg = nullptr;
+    return L;
+}
+
 extern "C" {
 // render_ops.hip
 int sahs_ray_bundle_launch(int H, int W, float fx, float fy, float cx, float cy, const float *c2w, int ld, float *ro, float *rd,
@@ -36,8 +72,8 @@ int sahs_stage1_loss_forward_launch(long N, const float *map_c, const float *map
 int sahs_conditioning_backward_launch(const float *flat, const float *audio, const float *grad_cond, float *grad_flat, float *grad_audio,
                                       hipStream_t stream);
 
-// The sources built once per model (sahs_model.hpp: SAHS_MODEL=0 no suffix, 1 suffix _nf, 2 suffix _ns).  A model build without one of
-// these launchers leaves its name undefined; capi.hip's table holds nullptr there (and the link, -z defs, fails on any other reference).
+// The sources built once per model (sahs_model.hpp: SAHS_MODEL=0 no suffix, 1 suffix _nf, 2 suffix _ns).  Every model build defines every
+// one of these; a forward launcher answers -2 or -3 for a mode its build does not have (and the link, -z defs, fails on a name left undefined).
 #define SAHS_DECLARE_MODEL(sfx)                                                                                                          \
     /* pack.hip */                                                                                                                       \
     long sahs_layout_param_count##sfx(void);                                                                                            \
@@ -47,57 +83,24 @@ int sahs_conditioning_backward_launch(const float *flat, const float *audio, con
     long sahs_layout_frame_words##sfx(void);                                                                                            \
     long sahs_layout_act_words##sfx(void);                                                                                              \
     long sahs_layout_executed_macs##sfx(int precision, int part);                                                                       \
-    int sahs_pack_weights_f32_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                       \
-    int sahs_pack_weights_bf16_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                      \
-    int sahs_pack_weights_bf16x3_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                    \
-    int sahs_fold_conditioning_launch##sfx(const float *flat, const float *audio, const float *pose, int pose_ld, float *frame,        \
+    int sahs_pack_weights_f32_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                        \
+    int sahs_pack_weights_bf16_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                       \
+    int sahs_pack_weights_bf16x3_launch##sfx(const float *flat, float *packed, hipStream_t stream);                                     \
+    int sahs_fold_conditioning_launch##sfx(const float *flat, const float *audio, const float *pose, int pose_ld, float *frame,         \
                                            hipStream_t stream);                                                                         \
     /* field_f32.hip */                                                                                                                  \
     int sahs_layout_act_part_words##sfx(int part);                                                                                      \
     int sahs_layout_act_part_col0##sfx(int part);                                                                                       \
     int sahs_layout_bits_part_words##sfx(int part);                                                                                     \
-    int sahs_field_forward_f32_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,       \
-                                           int ray_stride, const float *zvals, float *raw, float *dbg, float *actbuf, int num_cu,       \
-                                           hipStream_t stream);                                                                         \
-    int sahs_field_forward_f32_split_launch##sfx(const float *packed, const float *frame, int level, int mode, long P, int S,          \
-                                                 const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,          \
-                                                 int xw_row, int xw_col0, const int *src, float *actbuf, int num_cu,                    \
-                                                 hipStream_t stream);                                                                   \
-    int sahs_field_forward_f32_split_bits_launch##sfx(const float *packed, const float *frame, int level, int mode, long P, int S,     \
-                                                      const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,     \
-                                                      int xw_row, int xw_col0, const int *src, float *actbuf, uint32_t *bits,           \
-                                                      int num_cu, hipStream_t stream);                                                  \
     long sahs_field_f32_sparse_ws_bytes##sfx(long cap);                                                                                 \
     long sahs_field_f32_sparse_ring_slots##sfx(long P, int num_cu);                                                                     \
-    int sahs_field_forward_f32_sparse_launch##sfx(const float *packed, const float *frame, int level, int stage, long P, int S,        \
-                                                  const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,         \
-                                                  int xw_row, int xw_col0, const int *src, const float *noise, int has_bg, void *ws,    \
-                                                  long cap, int num_cu, hipStream_t stream);                                            \
+    int sahs_field_f32_launch##sfx(const FieldLaunch *launch, int mode);                                                                \
+    int sahs_field_f32_sparse_launch##sfx(const FieldLaunch *launch, int stage, const float *noise, int has_bg, void *ws, long cap);    \
     /* field_bf16w.hip */                                                                                                                \
     int sahs_bf16w_exact_leaky_state##sfx(int set);                                                                                     \
-    int sahs_field_forward_bf16w_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,     \
-                                             int ray_stride, const float *zvals, float *raw, float *dbg, int num_cu, hipStream_t stream); \
-    int sahs_field_forward_bf16w_split_launch##sfx(const float *packed, const float *frame, int level, int mode, long P, int S,        \
-                                                   const float *rays, int ray_stride, const float *zvals, float *raw, float *xw,        \
-                                                   int xw_row, int xw_col0, const int *src, int num_cu, hipStream_t stream);            \
-    /* field_bf16x3.hip */                                                                                                               \
-    int sahs_field_deform_bf16x3_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,     \
-                                             int ray_stride, const float *zvals, float *xw, int xw_row, int xw_col0, int num_cu,        \
-                                             hipStream_t stream);                                                                       \
-    int sahs_field_deform_bf16x3_save_launch##sfx(const float *packed, const float *frame, int level, long P, int S,                  \
-                                                  const float *rays, int ray_stride, const float *zvals, float *xw, int xw_row,         \
-                                                  int xw_col0, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream);          \
-    int sahs_field_radiance_bf16x3_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,   \
-                                               int ray_stride, float *raw, const float *xw, int xw_row, const int *src, int num_cu,     \
-                                               hipStream_t stream);                                                                     \
-    int sahs_field_radiance_bf16x3_save_launch##sfx(const float *packed, const float *frame, int level, long P, int S,                \
-                                                    const float *rays, int ray_stride, float *raw, const float *xw, int xw_row,         \
-                                                    const int *src, float *actbuf, uint32_t *bits, int num_cu, hipStream_t stream);     \
-    int sahs_field_forward_bf16x3_launch##sfx(const float *packed, const float *frame, int level, long P, int S, const float *rays,    \
-                                              int ray_stride, const float *zvals, float *raw, int num_cu, hipStream_t stream);          \
-    int sahs_field_forward_bf16x3_save_launch##sfx(const float *packed, const float *frame, int level, long P, int S,                  \
-                                                   const float *rays, int ray_stride, const float *zvals, float *raw, float *actbuf,    \
-                                                   uint32_t *bits, int num_cu, hipStream_t stream);                                     \
+    int sahs_field_bf16w_launch##sfx(const FieldLaunch *launch, int mode);                                                              \
+    /* field_bf16x3.hip */                                                                                                              \
+    int sahs_field_bf16x3_launch##sfx(const FieldLaunch *launch, int mode);                                                             \
     /* field_bwd.hip */                                                                                                                  \
     int sahs_bwd_gemm_precision_state##sfx(int set);                                                                                    \
     long sahs_field_backward_ws_words##sfx(long P);                                                                                     \
@@ -112,10 +115,10 @@ int sahs_conditioning_backward_launch(const float *flat, const float *audio, con
                                               float *grad_flat, float *grad_cond, float *ws, int num_cu, hipStream_t stream);           \
     /* field_bwd_chain.hip: the fused walk's data-gradient chains (split bf16 operands) */                                              \
     long sahs_bwd_chain_stream_hw##sfx(int part);                                                                                       \
-    int sahs_bwd_chain_pack_launch##sfx(const float *flat, void *stream_out, int level, int part, hipStream_t stream);                 \
-    int sahs_bwd_chain_rad_launch##sfx(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact,             \
+    int sahs_bwd_chain_pack_launch##sfx(const float *flat, void *stream_out, int level, int part, hipStream_t stream);                  \
+    int sahs_bwd_chain_rad_launch##sfx(const void *bstream, long P, const float *d_raw, const uint32_t *bits, float *dact,              \
                                        float *dgridf, float *din_a, float *din_b, int num_cu, hipStream_t stream);                      \
-    int sahs_bwd_chain_def_launch##sfx(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits,       \
+    int sahs_bwd_chain_def_launch##sfx(const void *bstream, long P, const float *xwg, const float *actbuf, const uint32_t *bits,        \
                                        float *dact, float *g3, float *dw4, int num_cu, hipStream_t stream);                             \
     /* field_bwd_chain_f32.hip: the same chains in exact fp32 products */                                                               \
     long sahs_bwd_chain_f32_stream_floats##sfx(int part);                                                                               \

@@ -2,7 +2,8 @@
 forward, saving, backward and render entry points for inputs that are rejected (or short-circuit) before any kernel runs.
 
 The values were recorded from the library as it stood before its dispatch moved into one table per model
-(csrc/capi.hip: kModels); a change to any of them is a change of the ABI's behaviour, not a refactor."""
+(csrc/capi.hip: kModels); a change to any of them is a change of the ABI's behaviour, not a refactor.  The sparse render entry's
+(SPARSE_CASES) were recorded at commit 0c084c6, before the field forward launchers took one argument block."""
 import pytest
 import torch
 
@@ -93,7 +94,10 @@ ARGS = {
                               "weights rgb_c disp_c acc_c rgb_f disp_f acc_f w_bg depth_f stream",
     "sahs_model_render_rays_rows": "model packed frame precision N rays ray_stride Sc nf lindisp white bg t_rand noise_c u noise_f z_c z_f raw "
                                    "weights rows row_ld xw src z_new stream",
+    "sahs_model_render_rays_rows_sparse": "model packed frame precision N rays ray_stride Sc nf lindisp white bg t_rand noise_c u noise_f z_c z_f "
+                                          "raw weights rows row_ld xw src z_new ws ws_bytes stream",
 }
+SPARSE = "sahs_model_render_rays_rows_sparse"      # (its cases are a list of their own, SPARSE_CASES: the first list's literal stays as recorded)
 # every argument not named in a case: a valid shape (one ray of one sample, level 0, mode 0, part 3, fp32) and, for pointers, null
 DEFAULTS = dict(model=0, level=0, N=1, S=1, P=1, ray_stride=8, precision=0, mode=0, part=3, xw_row=1, xw_col0=0, Sc=1, nf=0, lindisp=0,
                 white=0, row_ld=16)
@@ -104,13 +108,17 @@ ALL_PTRS = dict(packed=A, frame=A, rays=A, z=A, raw=A, act=A, bits=A, xw=A, src=
 
 def _call(L, name, kw):
     vals = dict(DEFAULTS, **kw)
+    if name == SPARSE:      # ws_bytes: what the ABI's query asks for the render's larger pass, `ws_records` records more (negative: fewer)
+        m = vals["model"]
+        record = (L.sahs_model_render_sparse_workspace_bytes(m, 128) - L.sahs_model_render_sparse_workspace_bytes(m, 0)) // 128
+        vals["ws_bytes"] = max(0, L.sahs_model_render_sparse_fused_workspace_bytes(m, vals["N"] * (vals["Sc"] + vals["nf"])) + record * vals.get("ws_records", 0))
     return getattr(L, name)(*[vals.get(a, None) for a in ARGS[name].split()])
 
 
 def _cases():
     """(function, arguments) of every return-code case, in a fixed order; `ptrs`: every pointer fabricated and aligned (then
     overridden per case)"""
-    MODEL_FNS = [n for n in ARGS if n.startswith("sahs_model_")]
+    MODEL_FNS = [n for n in ARGS if n.startswith("sahs_model_") and n != SPARSE]
     SAVES = ["sahs_model_field_forward_save", "sahs_model_field_forward_save_bits", "sahs_model_field_forward_save_bits_x3"]
     SPLIT_SAVES = ["sahs_model_field_forward_split_save", "sahs_model_field_forward_split_save_bits", "sahs_model_field_forward_split_save_bits_x3"]
     FWDS = ["sahs_model_field_forward", "sahs_model_field_forward_split"] + SAVES + SPLIT_SAVES
@@ -219,6 +227,10 @@ def _cases():
             cp("sahs_model_render_rays", model=m, precision=p, w_bg=0)
     cp("sahs_render_rays", nf=1, z_f=0); cp("sahs_render_rays", depth_f=0)
 
+    return _unique(cases)
+
+
+def _unique(cases):
     out, seen = [], set()
     for name, kw in cases:
         key = (name, tuple(sorted(kw.items())))
@@ -227,7 +239,36 @@ def _cases():
             out.append((name, kw))
     return out
 
+
+def _sparse_cases():
+    """the sparse render entry: the checks it shares with sahs_model_render_rays_rows, then those of its record workspace"""
+    cases = []
+    def c(**kw): cases.append((SPARSE, dict(dict(row_ld=36), **kw)))      # (36: a full row, SAHS_ROW_COLUMNS)
+    def cp(**kw): c(ptrs=True, **kw)
+    for m in (-1, 3):      # unknown model: before anything else
+        c(model=m); cp(model=m); c(model=m, N=0); cp(model=m, precision=1)
+    for m in (0, 1, 2):
+        c(model=m, N=0); cp(model=m, N=0); cp(model=m, N=0, nf=1, Sc=256)
+        c(model=m); c(model=m, nf=1)      # null pointers with a valid shape
+        cp(model=m); cp(model=m, nf=1); cp(model=m, nf=1, N=300, Sc=64, ws_records=1)      # a workspace that fits: the first launch
+        for key in ("rows", "packed", "frame", "rays", "z_c", "raw", "weights", "z_f", "ws", "xw", "src", "z_new", "bg"):
+            cp(model=m, nf=1, **{key: 0})
+        cp(model=m, z_f=0)
+        for key in ("packed", "frame", "raw", "xw", "ws", "rays", "z_c", "rows"):
+            cp(model=m, nf=1, **{key: M})
+        for kw in (dict(row_ld=35), dict(N=-1), dict(Sc=0), dict(nf=-1), dict(ray_stride=7), dict(nf=1, Sc=256), dict(nf=0, Sc=256), dict(nf=0, Sc=257)):
+            cp(model=m, **kw)
+        for p in (-1, 1, 2, 3, 4):      # no sparse branches in the other precisions: sahs_model_render_rays_rows answers
+            cp(model=m, precision=p, nf=1); cp(model=m, precision=p, nf=1, xw=0); cp(model=m, precision=p, nf=1, Sc=256); cp(model=m, precision=p, rows=0)
+            c(model=m, precision=p, N=0)
+        # a workspace one record short of its rings, coarse pass alone and both passes; none at all; a pass over 2^30 samples
+        cp(model=m, ws_records=-1); cp(model=m, nf=1, N=300, Sc=64, ws_records=-1); cp(model=m, ws_records=-10 ** 6)
+        cp(model=m, N=(1 << 22) + 1, Sc=256); cp(model=m, N=(1 << 23), Sc=128, nf=1); cp(model=m, N=(1 << 22), Sc=256)
+    return _unique(cases)
+
+
 CASES = _cases()
+SPARSE_CASES = _sparse_cases()
 # one character per case: the code returned, or L = validation passed and a launch was attempted (no GPU here: a HIP error, 100 + e)
 EXPECTED_CODES = (
     "3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 4 4 4 4 4 4 0 4 4 4 4 4 4 0 4 4 4 4 4 4 4 4 4 4 4 4 4 4 1 L 1 4 1 4 4 4 4 4 4 4 4 4 "
@@ -246,9 +287,16 @@ EXPECTED_CODES = (
     "1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 ")
 
 
-def _codes(L, fabricated):
+EXPECTED_SPARSE_CODES = (
+    "3 3 3 3 3 3 3 3 0 0 0 1 1 L L L 1 1 1 1 1 1 1 1 1 L L L L L 1 1 1 1 1 L L L 1 1 1 1 1 1 L 1 L L L 1 0 L L 1 1 0 L L L 1 0 L 1 1 1 0 L L L 1 "
+    "0 5 5 5 5 5 L 0 0 0 1 1 L L L 1 1 1 1 1 1 1 1 1 L L L L L 1 1 1 1 1 L L L 1 1 1 1 1 1 L 1 L L L 1 0 L 1 1 1 0 L L L 1 0 L 1 1 1 0 L L L 1 0 "
+    "5 5 5 5 5 L 0 0 0 1 1 L L L 1 1 1 1 1 1 1 1 1 L L L L L 1 1 1 1 1 L L L 1 1 1 1 1 1 L 1 L L L 1 0 L L L 1 0 L L L 1 0 L L L 1 0 L L L 1 0 5 "
+    "5 5 5 5 L ")
+
+
+def _codes(L, fabricated, cases):
     out = []
-    for name, kw in CASES:
+    for name, kw in cases:
         kw = dict(kw)
         if kw.pop("ptrs", False) != fabricated:
             continue
@@ -259,9 +307,10 @@ def _codes(L, fabricated):
     return out
 
 
-def _check(fabricated):
-    want = [w for (_, kw), w in zip(CASES, EXPECTED_CODES.split()) if bool(kw.get("ptrs")) == fabricated]
-    got = _codes(pkg("_lib").lib(), fabricated)
+def _check(fabricated, cases=CASES, expected=EXPECTED_CODES):
+    assert len(cases) == len(expected.split())
+    want = [w for (_, kw), w in zip(cases, expected.split()) if bool(kw.get("ptrs")) == fabricated]
+    got = _codes(pkg("_lib").lib(), fabricated, cases)
     assert len(got) == len(want)
     bad = ["%s(%s): %s, expected %s" % (n, kw, g, w) for (n, kw, g), w in zip(got, want) if g != w]
     assert not bad, "\n".join(bad[:20])
@@ -276,3 +325,13 @@ def test_return_codes_fabricated_pointers():
     if torch.cuda.is_available():
         pytest.skip("fabricated device pointers are only passed where no GPU can run a kernel")
     _check(True)
+
+
+def test_sparse_render_return_codes_null_pointers():
+    _check(False, SPARSE_CASES, EXPECTED_SPARSE_CODES)
+
+
+def test_sparse_render_return_codes_fabricated_pointers():
+    if torch.cuda.is_available():
+        pytest.skip("fabricated device pointers are only passed where no GPU can run a kernel")
+    _check(True, SPARSE_CASES, EXPECTED_SPARSE_CODES)

@@ -80,6 +80,8 @@ def test_new_symbols_are_exported():
     L = pkg("_lib")
     for name in ("sahs_model_field_forward_save_bits_x3", "sahs_model_field_forward_split_save_bits_x3"):
         assert name in L.SIGNATURES and hasattr(L.lib(), name)
-    for sym in ("sahs_field_radiance_bf16x3_launch_nf", "sahs_field_radiance_bf16x3_save_launch_nf", "sahs_field_deform_bf16x3_save_launch_nf",
-                "sahs_field_forward_bf16x3_launch_ns", "sahs_field_forward_bf16x3_save_launch_ns"):
-        assert hasattr(L.lib(), sym), sym
+    # every forward launcher the dispatch table (csrc/capi.hip: kModels) holds, for every model build: each build defines all of them
+    for sfx in ("", "_nf", "_ns"):
+        for family in ("sahs_field_f32_launch", "sahs_field_f32_sparse_launch", "sahs_field_f32_sparse_ws_bytes", "sahs_field_f32_sparse_ring_slots",
+                       "sahs_field_bf16w_launch", "sahs_field_bf16x3_launch"):
+            assert hasattr(L.lib(), family + sfx), family + sfx
