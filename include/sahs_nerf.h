@@ -360,10 +360,26 @@ int sahs_adam_step(float *params, const float *grad, float *exp_avg, float *exp_
  *   out = lrelu_slope( InstanceNorm2d(x; eps, biased variance, no affine) * (1 + gamma) + beta )
  * over `planes` = N*C contiguous planes of `hw` = H*W floats each (NCHW); gamma, beta, out have x's shape; slope 1 = no activation;
  * stats: sahs_spade_modulate_workspace_words(planes) floats of workspace (per plane: chunk sums and chunk sums of squares about the mean).  The convolutions that produce gamma / beta stay library
- * calls (MIOpen through PyTorch): sahs-deformable-nerf_amd/spade.py. */
+ * calls (MIOpen through PyTorch): sahs-deformable-nerf_amd/spade.py.  A plane is one gridDim.y slot of every launch: planes <= 65535
+ * (more is refused with a non-zero return code before anything is launched). */
 long sahs_spade_modulate_workspace_words(long planes);
 int sahs_spade_modulate(long planes, long hw, const float *x, const float *gamma, const float *beta, float eps, float slope, float *out,
                         float *stats, void *stream);
+
+/* Its backward (Stage-II refiner training): given grad_out = dL/d out, with mean, r = 1 / sqrt(var + eps), xh = (x - mean) * r per plane,
+ *   dy = grad_out * (out > 0 ? 1 : slope)      dbeta = dy      dgamma = dy * xh
+ *   dx = r * (dxh - mean(dxh) - xh * mean(dxh * xh)),   dxh = dy * (1 + gamma),   means over the plane's hw elements.
+ * x, gamma, out: what sahs_spade_modulate read and wrote; stats: its workspace exactly as that call left it for this x (mean and r are
+ * re-formed from it as the forward formed them).  The activation mask is taken from `out` (out > 0 exactly when the pre-activation is, for
+ * slope >= 0; at 0 the factor is slope, as in ATen's leaky_relu_backward); out may be null only when slope == 1, where it is not read.
+ * slope < 0 is invalid here (the forward accepts it).  Each of dx, dgamma, dbeta may be null (not wanted), not all three; work:
+ * sahs_spade_modulate_backward_workspace_words(planes) floats, needed for dx.  planes <= 65535 (gridDim.y; more is an invalid argument).
+ * Two launches (chunk sums, then apply), no atomics: results are bit-reproducible.  16-byte accesses where hw % 4 == 0 and every
+ * pointer given is 16-byte aligned, element by element otherwise. */
+long sahs_spade_modulate_backward_workspace_words(long planes);
+int sahs_spade_modulate_backward(long planes, long hw, const float *x, const float *gamma, const float *out, const float *stats,
+                                 const float *grad_out, float eps, float slope, float *dx, float *dgamma, float *dbeta, float *work,
+                                 void *stream);
 
 /* ---- launch probe (opt-in measurement aid; the one exception to "never synchronises") ----
  * While armed on the calling thread, every FIELD-kernel launch the library makes (from any entry point above) is bracketed by two HIP

@@ -287,6 +287,22 @@ int sahs_spade_modulate(long planes, long hw, const float *x, const float *gamma
     return e ? hip_fail("sahs_spade_modulate", e) : 0;
 }
 
+long sahs_spade_modulate_backward_workspace_words(long planes) { return planes > 0 ? sahs_spade_stats_words(planes) : 0; }
+
+int sahs_spade_modulate_backward(long planes, long hw, const float *x, const float *gamma, const float *out, const float *stats,
+                                 const float *grad_out, float eps, float slope, float *dx, float *dgamma, float *dbeta, float *work, void *stream)
+{
+    if (planes == 0 || hw == 0) return 0;
+    REQUIRE(planes > 0 && hw > 0 && x && gamma && stats && grad_out && eps > 0.0f, "sahs_spade_modulate_backward");
+    REQUIRE(planes <= 65535, "sahs_spade_modulate_backward(planes <= 65535: one plane per gridDim.y)");
+    REQUIRE(slope >= 0.0f && (out || slope == 1.0f), "sahs_spade_modulate_backward(slope >= 0; out may be null only for slope 1)");
+    REQUIRE(dx || dgamma || dbeta, "sahs_spade_modulate_backward(at least one of dx, dgamma, dbeta)");
+    REQUIRE(work || !dx, "sahs_spade_modulate_backward(dx needs the workspace)");
+    int e = sahs_spade_modulate_backward_launch(planes, hw, x, gamma, slope == 1.0f ? nullptr : out, stats, grad_out, eps, slope, dx, dgamma,
+                                                dbeta, work, (hipStream_t)stream);
+    return e ? hip_fail("sahs_spade_modulate_backward", e) : 0;
+}
+
 int sahs_composite_forward_rows(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
                                 const float *bg, int white_background, float *weights, float *rows, int row_ld, int fine_pass, void *stream)
 {

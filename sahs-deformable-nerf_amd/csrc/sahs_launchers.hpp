@@ -58,6 +58,9 @@ int sahs_ray_uniforms_launch(unsigned long long seed, int stream_id, long ray0, 
 long sahs_spade_stats_words(long planes);
 int sahs_spade_modulate_launch(long planes, long hw, const float *x, const float *gamma, const float *beta, float eps, float slope, float *out,
                                float *stats, hipStream_t stream);
+int sahs_spade_modulate_backward_launch(long planes, long hw, const float *x, const float *gamma, const float *out, const float *stats,
+                                        const float *grad, float eps, float slope, float *dx, float *dgamma, float *dbeta, float *work,
+                                        hipStream_t stream);
 // optim.hip (w1 = 1 - beta1, w2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): formed in double by the caller)
 int sahs_adam_step_launch(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float w1, float beta2, float w2,
                           float step_size, float bc2_sqrt, float eps, float grad_scale, hipStream_t stream);

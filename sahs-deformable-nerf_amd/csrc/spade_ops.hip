@@ -98,9 +98,153 @@ __global__ void __launch_bounds__(256) spade_modulate_kernel(long hw, const floa
     }
 }
 
+// ---- backward of the fused modulation (training of the Stage-II refiner) ----
+//   dy = g * (out > 0 ? 1 : slope)     dbeta = dy     dgamma = dy * xh     dxh = dy * (1 + gamma)
+//   dx = rstd * (dxh - mean(dxh) - xh * mean(dxh * xh))                     xh = (x - mean) * rstd
+// The activation mask is read from the forward's OUTPUT (out > 0 exactly when y > 0 for slope >= 0; at 0 it gives slope, as ATen's
+// leaky_relu_backward does), so it is the forward's own whatever the compiler contracted there; out == nullptr: slope 1, dy = g.
+// Two launches shaped like the forward's, no atomics: a sums pass over (chunk, plane) workgroups writes each chunk's sum of dxh and of
+// dxh * xh to work[plane][chunk][2], the apply pass re-adds the chunks in order.  16 B read per element in each pass, 12 B written.
+
+// the plane's mean and 1 / sqrt(var + eps) from the forward's statistics workspace, formed as spade_modulate_kernel forms them
+__device__ __forceinline__ void plane_norm(const float *pp, long hw, float eps, float &mean, float &rstd)
+{
+    mean = plane_mean(pp, hw);
+    float var = 0.0f;
+#pragma unroll
+    for (int c = 0; c < SPADE_CHUNKS; ++c) var += pp[2 * c + 1];
+    rstd = 1.0f / sqrtf(var / (float)hw + eps);
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) spade_backward_sums_kernel(long hw, const float *__restrict__ x, const float *__restrict__ gamma,
+                                                                  const float *__restrict__ out, const float *__restrict__ stats,
+                                                                  const float *__restrict__ grad, float eps, float slope,
+                                                                  float *__restrict__ work)
+{
+    __shared__ float red[4];
+    const long plane = blockIdx.y, base = plane * hw;
+    float mean, rstd;
+    plane_norm(stats + plane * (2 * SPADE_CHUNKS), hw, eps, mean, rstd);
+    const long n = VEC ? hw / 4 : hw, per = (n + SPADE_CHUNKS - 1) / SPADE_CHUNKS;
+    const long lo = blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    float s0 = 0.0f, s1 = 0.0f;
+    for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        if (VEC) {
+            const f32x4 gv = reinterpret_cast<const f32x4 *>(grad + base)[i], xv = reinterpret_cast<const f32x4 *>(x + base)[i],
+                        mv = reinterpret_cast<const f32x4 *>(gamma + base)[i];
+            f32x4 ov = {1.0f, 1.0f, 1.0f, 1.0f};
+            if (out) ov = reinterpret_cast<const f32x4 *>(out + base)[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float dxh = (ov[k] > 0.0f ? gv[k] : gv[k] * slope) * (1.0f + mv[k]);
+                s0 += dxh;
+                s1 += dxh * ((xv[k] - mean) * rstd);
+            }
+        } else {
+            const float g = grad[base + i], dy = (!out || out[base + i] > 0.0f) ? g : g * slope;
+            const float dxh = dy * (1.0f + gamma[base + i]);
+            s0 += dxh;
+            s1 += dxh * ((x[base + i] - mean) * rstd);
+        }
+    }
+    s0 = block_sum256(s0, red);
+    s1 = block_sum256(s1, red);
+    if (threadIdx.x == 0) {
+        float *wp = work + plane * (2 * SPADE_CHUNKS) + 2 * blockIdx.x;
+        wp[0] = s0;
+        wp[1] = s1;
+    }
+}
+
+// dx, dgamma, dbeta: each written where its pointer is not null; work is read only for dx
+template <bool VEC>
+__global__ void __launch_bounds__(256) spade_backward_apply_kernel(long hw, const float *__restrict__ x, const float *__restrict__ gamma,
+                                                                   const float *__restrict__ out, const float *__restrict__ stats,
+                                                                   const float *__restrict__ grad, const float *__restrict__ work, float eps,
+                                                                   float slope, float *__restrict__ dx, float *__restrict__ dgamma,
+                                                                   float *__restrict__ dbeta)
+{
+    const long plane = blockIdx.y, base = plane * hw;
+    float mean, rstd;
+    plane_norm(stats + plane * (2 * SPADE_CHUNKS), hw, eps, mean, rstd);
+    float m0 = 0.0f, m1 = 0.0f;
+    if (dx) {
+        const float *wp = work + plane * (2 * SPADE_CHUNKS);
+#pragma unroll
+        for (int c = 0; c < SPADE_CHUNKS; ++c) { m0 += wp[2 * c]; m1 += wp[2 * c + 1]; }
+        m0 /= (float)hw;
+        m1 /= (float)hw;
+    }
+    if (VEC) {
+        const long n4 = hw >> 2;
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+            const f32x4 gv = reinterpret_cast<const f32x4 *>(grad + base)[i], xv = reinterpret_cast<const f32x4 *>(x + base)[i];
+            f32x4 ov = {1.0f, 1.0f, 1.0f, 1.0f}, mv = {0.0f, 0.0f, 0.0f, 0.0f}, dy, xh;
+            if (out) ov = reinterpret_cast<const f32x4 *>(out + base)[i];
+            if (dx) mv = reinterpret_cast<const f32x4 *>(gamma + base)[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                dy[k] = ov[k] > 0.0f ? gv[k] : gv[k] * slope;
+                xh[k] = (xv[k] - mean) * rstd;
+            }
+            if (dbeta) reinterpret_cast<f32x4 *>(dbeta + base)[i] = dy;
+            if (dgamma) {
+                f32x4 o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = dy[k] * xh[k];
+                reinterpret_cast<f32x4 *>(dgamma + base)[i] = o;
+            }
+            if (dx) {
+                f32x4 o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = rstd * ((dy[k] * (1.0f + mv[k]) - m0) - xh[k] * m1);
+                reinterpret_cast<f32x4 *>(dx + base)[i] = o;
+            }
+        }
+    } else {
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += (long)gridDim.x * blockDim.x) {
+            const float g = grad[base + i], dy = (!out || out[base + i] > 0.0f) ? g : g * slope;
+            const float xh = (x[base + i] - mean) * rstd;
+            if (dbeta) dbeta[base + i] = dy;
+            if (dgamma) dgamma[base + i] = dy * xh;
+            if (dx) dx[base + i] = rstd * ((dy * (1.0f + gamma[base + i]) - m0) - xh * m1);
+        }
+    }
+}
+
 }  // namespace sahs
 
+// the modulate-shaped grid: a 256-thread workgroup per 256 elements (or vectors) of a plane, capped at ~8 k workgroups in all
+static dim3 spade_plane_grid(long per, long planes)
+{
+    long bx = (per + 255) / 256;
+    const long cap = (8192 + planes - 1) / planes;
+    if (bx > cap) bx = cap;
+    if (bx < 1) bx = 1;
+    return dim3((unsigned)bx, (unsigned)planes);
+}
+
 extern "C" long sahs_spade_stats_words(long planes) { return planes * 2 * sahs::SPADE_CHUNKS; }
+
+extern "C" int sahs_spade_modulate_backward_launch(long planes, long hw, const float *x, const float *gamma, const float *out, const float *stats,
+                                                   const float *grad, float eps, float slope, float *dx, float *dgamma, float *dbeta, float *work,
+                                                   hipStream_t stream)
+{
+    if (planes <= 0 || hw <= 0) return 0;
+    if (planes > 65535) return -2;      // gridDim.y
+    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };      // (a null pointer is never dereferenced)
+    const bool vec = (hw % 4 == 0) && al(x) && al(gamma) && al(out) && al(grad) && al(dx) && al(dgamma) && al(dbeta);
+    if (dx) {
+        const dim3 sgrid(sahs::SPADE_CHUNKS, (unsigned)planes);
+        if (vec) sahs::spade_backward_sums_kernel<true><<<sgrid, 256, 0, stream>>>(hw, x, gamma, out, stats, grad, eps, slope, work);
+        else sahs::spade_backward_sums_kernel<false><<<sgrid, 256, 0, stream>>>(hw, x, gamma, out, stats, grad, eps, slope, work);
+    }
+    const dim3 grid = spade_plane_grid(vec ? hw / 4 : hw, planes);
+    if (vec) sahs::spade_backward_apply_kernel<true><<<grid, 256, 0, stream>>>(hw, x, gamma, out, stats, grad, work, eps, slope, dx, dgamma, dbeta);
+    else sahs::spade_backward_apply_kernel<false><<<grid, 256, 0, stream>>>(hw, x, gamma, out, stats, grad, work, eps, slope, dx, dgamma, dbeta);
+    return (int)hipGetLastError();
+}
 
 extern "C" int sahs_spade_modulate_launch(long planes, long hw, const float *x, const float *gamma, const float *beta, float eps, float slope,
                                           float *out, float *stats, hipStream_t stream)
@@ -114,12 +258,7 @@ extern "C" int sahs_spade_modulate_launch(long planes, long hw, const float *x, 
         if (vec) sahs::instance_stats_kernel<true><<<sgrid, 256, 0, stream>>>(hw, x, stats, pass);
         else sahs::instance_stats_kernel<false><<<sgrid, 256, 0, stream>>>(hw, x, stats, pass);
     }
-    const long per = vec ? hw / 4 : hw;
-    long bx = (per + 255) / 256;
-    const long cap = (8192 + planes - 1) / planes;      // ~8 k workgroups in all
-    if (bx > cap) bx = cap;
-    if (bx < 1) bx = 1;
-    const dim3 grid((unsigned)bx, (unsigned)planes);
+    const dim3 grid = spade_plane_grid(vec ? hw / 4 : hw, planes);
     if (vec) sahs::spade_modulate_kernel<true><<<grid, 256, 0, stream>>>(hw, x, gamma, beta, stats, eps, slope, out);
     else sahs::spade_modulate_kernel<false><<<grid, 256, 0, stream>>>(hw, x, gamma, beta, stats, eps, slope, out);
     return (int)hipGetLastError();

@@ -8,6 +8,7 @@ BY NAME (_save_named / _load_named; None = absent).  Its backward (_RenderBackwa
 issues the same steps on one stream or, for the per-layer walks of "shared", pairwise on two, and returns gradients for the flat parameter
 buffer and the driving input.  Importance resampling is not differentiated (the reference detaches it, train_utils.py:164).  The stand-alone
 seams are differentiable too: ``FieldFn`` behind model(level, x, driving, pose), ``CompositeFn`` behind volume_render_radiance_field.
+Stage II: ``SpadeModulateFn`` behind spade_modulate, taken only when one of its tensors needs a gradient.
 """
 import ctypes
 import os
@@ -355,8 +356,8 @@ def render_rays_rows(packed, frame, rays, num_coarse, num_fine, rows, precision=
     return rows
 
 
-def spade_modulate(x, gamma, beta, eps=1e-5, slope=1.0):
-    """lrelu_slope(InstanceNorm2d(x) * (1 + gamma) + beta) for NCHW tensors of one shape, fused (include/sahs_nerf.h: sahs_spade_modulate)."""
+def _spade_modulate_forward(x, gamma, beta, eps, slope):
+    """-> (x, gamma as the kernel read them (contiguous), out, the statistics workspace the launch left)."""
     x, gamma, beta = _req(x, "x"), _req(gamma, "gamma"), _req(beta, "beta")
     if x.dim() != 4 or gamma.shape != x.shape or beta.shape != x.shape:
         raise _lib.SahsError("spade_modulate: x, gamma, beta must be NCHW tensors of one shape, got %s %s %s" % (tuple(x.shape), tuple(gamma.shape), tuple(beta.shape)))
@@ -364,7 +365,16 @@ def spade_modulate(x, gamma, beta, eps=1e-5, slope=1.0):
     out = torch.empty_like(x)
     stats = torch.empty(int(_lib.lib().sahs_spade_modulate_workspace_words(planes)), dtype=torch.float32, device=x.device)
     check(_lib.lib().sahs_spade_modulate(planes, hw, _p(x), _p(gamma), _p(beta), float(eps), float(slope), _p(out), _p(stats), _stream()), "sahs_spade_modulate")
-    return out
+    return x, gamma, out, stats
+
+
+def spade_modulate(x, gamma, beta, eps=1e-5, slope=1.0):
+    """lrelu_slope(InstanceNorm2d(x) * (1 + gamma) + beta) for NCHW tensors of one shape, fused (include/sahs_nerf.h: sahs_spade_modulate).
+    Differentiable (SpadeModulateFn: sahs_spade_modulate_backward) when grad mode is on and one of the three tensors requires a gradient;
+    with plain tensors it is the two launches of the forward alone, whatever the grad mode."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, gamma, beta)):
+        return SpadeModulateFn.apply(x, gamma, beta, float(eps), float(slope))
+    return _spade_modulate_forward(x, gamma, beta, eps, slope)[2]
 
 
 def adam_step(params, grad, exp_avg, exp_avg_sq, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, grad_scale=1.0):
@@ -695,6 +705,39 @@ class CompositeFn(torch.autograd.Function):
         if s.bg is not None and g_rgb is not None:     # the last sample's 15 channels are used verbatim (:28-35): d = w_last * d_rgb
             d_raw[:, -1, :15] += s.w_last[:, None] * g_rgb
         return d_raw, None, None, None, None, None
+
+
+class SpadeModulateFn(torch.autograd.Function):
+    """spade_modulate as a differentiable op (Stage-II refiner training): the forward's two launches, and a two-launch fused backward
+    (include/sahs_nerf.h: sahs_spade_modulate_backward) in place of the six autograd nodes of the written-out formula.  Saved: x, gamma,
+    the output -- the activation mask is read from it -- and the forward's statistics workspace; beta is not needed.  Gradients are
+    formed only for the inputs that ask for one.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, slope):
+        if not slope >= 0.0:
+            raise _lib.SahsError("spade_modulate: the differentiable path needs slope >= 0 (the activation mask is read from the output), got %r" % (slope,))
+        x, gamma, out, stats = _spade_modulate_forward(x, gamma, beta, eps, slope)
+        _save_named(ctx, x=x.detach(), gamma=gamma.detach(), out=out, stats=stats)
+        ctx.eps, ctx.slope = eps, slope
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        s = _load_named(ctx)
+        grad_out = _req(grad_out, "grad_out")      # (contiguous: out.sum().backward() hands over a stride-0 expansion)
+        if grad_out.shape != s.x.shape:
+            raise _lib.SahsError("SpadeModulateFn.backward: gradient of shape %s for an output of shape %s" % (tuple(grad_out.shape), tuple(s.x.shape)))
+        planes, hw = s.x.shape[0] * s.x.shape[1], s.x.shape[2] * s.x.shape[3]
+        dx, dgamma, dbeta = (torch.empty_like(s.x) if need else None for need in ctx.needs_input_grad[:3])
+        work = None
+        if dx is not None:
+            work = torch.empty(int(_lib.lib().sahs_spade_modulate_backward_workspace_words(planes)), dtype=torch.float32, device=s.x.device)
+        check(_lib.lib().sahs_spade_modulate_backward(planes, hw, _p(s.x), _p(s.gamma), _p(s.out), _p(s.stats), _p(grad_out), float(ctx.eps),
+                                                      float(ctx.slope), _p(dx), _p(dgamma), _p(dbeta), _p(work), _stream()),
+              "sahs_spade_modulate_backward")
+        return dx, dgamma, dbeta, None, None
 
 
 class FieldFn(torch.autograd.Function):

@@ -4,8 +4,10 @@ reference's ``nerf/_init_spade.py`` (:114-160, :235-282) with the reference's ``
 
 What runs where: the 3x3 convolutions are library work -- ``torch.nn.functional.conv2d`` is MIOpen on ROCm -- and
 a hand-written convolution would buy nothing here; the normalise / modulate / activate chain between them, which the reference runs as
-six elementwise passes, is ONE fused HIP kernel behind a statistics pass (``ops.spade_modulate``).  Inference only: the refiner's
-training (GAN losses, discriminator, VGG features) is outside the hot-path scope.
+six elementwise passes, is ONE fused HIP kernel behind a statistics pass (``ops.spade_modulate``).  It is differentiable -- a fused
+two-launch backward in place of six autograd nodes per SPADE layer -- so the generators train: ``refine_step`` is the step of the
+reference's train_get_texture_photo.py / train_get_texture_photo_audio.py (clamp, MSE, Adam; the discriminator and the VGG loss that
+_init_spade.py also defines are never called by those loops and are not built).
 """
 import torch
 import torch.nn as nn
@@ -60,8 +62,6 @@ class SPADELayer(nn.Module):
 
     def forward(self, x, F_id, _slope=1.0):
         """_slope (not in the reference): the LeakyReLU slope of the SPADEBlock that follows, fused into the modulate kernel."""
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("the fused SPADE modulation is inference-only: call under torch.no_grad()")
         F_id = F_id.nearest(x.shape[-2:]) if isinstance(F_id, TiledCodeMap) else F.interpolate(F_id, size=x.shape[-2:], mode="nearest")
         hidden = self.mlp_shared(F_id)
         return ops.spade_modulate(x, self.conv_gamma(hidden), self.conv_beta(hidden), eps=self.EPS, slope=_slope)
@@ -171,7 +171,7 @@ class RefineNetwork(nn.Module):
 
 class Generator(nn.Module):
     """_init_spade.py:315-325: the Stage-II generator G(I_src, I_raw) of eval_get_texture_photo_audio.py:154 -- identity features of the
-    source image modulate the refinement of the Stage-I render.  Inference only (see SPADELayer)."""
+    source image modulate the refinement of the Stage-I render."""
 
     def __init__(self):
         super().__init__()
@@ -203,7 +203,8 @@ class AudioNet(nn.Module):
 
 class Generator_audio(nn.Module):
     """_init_spade.py:359-372: G(I_src, I_raw, audio window) of eval_get_texture_photo_audio.py:156 -- the deepest identity map is replaced by
-    the audio code tiled over a 256 x 64 x 4096 map (TiledCodeMap: never materialised here).  Inference only (see SPADELayer)."""
+    the audio code tiled over a 256 x 64 x 4096 map (TiledCodeMap: never materialised here; its ``nearest`` is an index, an expand and a
+    copy, so the AudioNet trains through it)."""
 
     def __init__(self):
         super().__init__()
@@ -215,3 +216,25 @@ class Generator_audio(nn.Module):
         fid1, fid2, _ = self.idencoder(I_src)
         code = self.AudioNet(driving_data.unsqueeze(0))                       # (1, 64)
         return self.refine_network(I_raw, fid1, fid2, TiledCodeMap(code, IdEncoder.WIDTHS[2], 64, 64))
+
+
+def refine_learning_rate(cfg, epoch):
+    """train_get_texture_photo.py:147-155: ``texture_refine.lr_G`` for the first ``texture_refine.epochs`` epochs, then linearly to zero
+    over ``texture_refine.epochs_decay`` more (the caller sets it on the optimiser's parameter groups at the start of each epoch)."""
+    t = cfg.texture_refine
+    if epoch < t.epochs:
+        return t.lr_G
+    return t.lr_G / t.epochs_decay * (t.epochs + t.epochs_decay - epoch)
+
+
+def refine_step(G, optimizer, I_src, I_raw, target, driving=None):
+    """One training step of the Stage-II generator, train_get_texture_photo.py:168-179 (``driving`` = the audio window of
+    train_get_texture_photo_audio.py:143-192 for Generator_audio): MSE between the clamped output and the target frame, backward,
+    optimiser step.  Returns the loss (a 0-d tensor; no synchronisation here).  The caller does ``G.train()``, the data loading and the
+    learning-rate schedule, as with training.train_step."""
+    optimizer.zero_grad()
+    fake = G(I_src, I_raw) if driving is None else G(I_src, I_raw, driving)
+    loss = F.mse_loss(fake.clamp(0, 1), target)
+    loss.backward()
+    optimizer.step()
+    return loss.detach()
