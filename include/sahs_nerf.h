@@ -381,6 +381,22 @@ int sahs_spade_modulate_backward(long planes, long hw, const float *x, const flo
                                  const float *grad_out, float eps, float slope, float *dx, float *dgamma, float *dbeta, float *work,
                                  void *stream);
 
+/* The same two calls with bf16 tensors (the refiner under torch.autocast, where the convolutions produce bf16): x, gamma, beta, out,
+ * grad_out, dx, dgamma, dbeta hold bf16 bit patterns (2 bytes per element; 10 B of traffic per element forward and 22 B backward, half
+ * of the fp32 calls').  stats and work stay fp32, with the sizes the *_workspace_words functions above return, and the stats a
+ * sahs_spade_modulate_bf16 call left are what sahs_spade_modulate_backward_bf16 reads (never mix them with the fp32 calls': the
+ * statistics are those of another tensor).  All arithmetic is fp32 -- operands are widened on load, the sums, mean, r and the two
+ * backward means are formed as the fp32 calls form them -- and each result is rounded to bf16 once, to nearest even, on store; the
+ * activation mask is out > 0 on the stored bf16 value.  Arguments and refusals as for sahs_spade_modulate_backward, in BOTH calls:
+ * planes <= 65535 (more is an invalid argument whose message names the limit), and for the backward slope >= 0, out null only for
+ * slope 1, at least one of dx / dgamma / dbeta, work for dx.  Access width: 16 bytes (8 bf16) per operand and thread where hw % 8 == 0
+ * and every pointer given is 16-byte aligned; element by element otherwise.  Two launches each, no atomics, bit-reproducible. */
+int sahs_spade_modulate_bf16(long planes, long hw, const unsigned short *x, const unsigned short *gamma, const unsigned short *beta, float eps,
+                             float slope, unsigned short *out, float *stats, void *stream);
+int sahs_spade_modulate_backward_bf16(long planes, long hw, const unsigned short *x, const unsigned short *gamma, const unsigned short *out,
+                                      const float *stats, const unsigned short *grad_out, float eps, float slope, unsigned short *dx,
+                                      unsigned short *dgamma, unsigned short *dbeta, float *work, void *stream);
+
 /* ---- launch probe (opt-in measurement aid; the one exception to "never synchronises") ----
  * While armed on the calling thread, every FIELD-kernel launch the library makes (from any entry point above) is bracketed by two HIP
  * events recorded on the launch stream, up to `capacity` launches (further ones are counted as dropped and run unprobed).

@@ -79,6 +79,8 @@ SIGNATURES = {
     "sahs_spade_modulate": (_I, [_L, _L, _P, _P, _P, _F, _F, _P, _P, _P]),
     "sahs_spade_modulate_backward_workspace_words": (_L, [_L]),
     "sahs_spade_modulate_backward": (_I, [_L, _L, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "sahs_spade_modulate_bf16": (_I, [_L, _L, _P, _P, _P, _F, _F, _P, _P, _P]),
+    "sahs_spade_modulate_backward_bf16": (_I, [_L, _L, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "sahs_probe_arm": (_I, [_I]),
     "sahs_probe_disarm": (_I, []),
     "sahs_probe_count": (_I, []),

@@ -303,6 +303,32 @@ int sahs_spade_modulate_backward(long planes, long hw, const float *x, const flo
     return e ? hip_fail("sahs_spade_modulate_backward", e) : 0;
 }
 
+// the bf16 forms (tensors as bf16 bit patterns; stats / work stay fp32): both refuse by name what the fp32 backward refuses
+int sahs_spade_modulate_bf16(long planes, long hw, const unsigned short *x, const unsigned short *gamma, const unsigned short *beta, float eps,
+                             float slope, unsigned short *out, float *stats, void *stream)
+{
+    if (planes == 0 || hw == 0) return 0;
+    REQUIRE(planes > 0 && hw > 0 && x && gamma && beta && out && stats && eps > 0.0f, "sahs_spade_modulate_bf16");
+    REQUIRE(planes <= 65535, "sahs_spade_modulate_bf16(planes <= 65535: one plane per gridDim.y)");
+    int e = sahs_spade_modulate_bf16_launch(planes, hw, x, gamma, beta, eps, slope, out, stats, (hipStream_t)stream);
+    return e ? hip_fail("sahs_spade_modulate_bf16", e) : 0;
+}
+
+int sahs_spade_modulate_backward_bf16(long planes, long hw, const unsigned short *x, const unsigned short *gamma, const unsigned short *out,
+                                      const float *stats, const unsigned short *grad_out, float eps, float slope, unsigned short *dx,
+                                      unsigned short *dgamma, unsigned short *dbeta, float *work, void *stream)
+{
+    if (planes == 0 || hw == 0) return 0;
+    REQUIRE(planes > 0 && hw > 0 && x && gamma && stats && grad_out && eps > 0.0f, "sahs_spade_modulate_backward_bf16");
+    REQUIRE(planes <= 65535, "sahs_spade_modulate_backward_bf16(planes <= 65535: one plane per gridDim.y)");
+    REQUIRE(slope >= 0.0f && (out || slope == 1.0f), "sahs_spade_modulate_backward_bf16(slope >= 0; out may be null only for slope 1)");
+    REQUIRE(dx || dgamma || dbeta, "sahs_spade_modulate_backward_bf16(at least one of dx, dgamma, dbeta)");
+    REQUIRE(work || !dx, "sahs_spade_modulate_backward_bf16(dx needs the workspace)");
+    int e = sahs_spade_modulate_backward_bf16_launch(planes, hw, x, gamma, slope == 1.0f ? nullptr : out, stats, grad_out, eps, slope, dx,
+                                                     dgamma, dbeta, work, (hipStream_t)stream);
+    return e ? hip_fail("sahs_spade_modulate_backward_bf16", e) : 0;
+}
+
 int sahs_composite_forward_rows(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
                                 const float *bg, int white_background, float *weights, float *rows, int row_ld, int fine_pass, void *stream)
 {

@@ -61,6 +61,12 @@ int sahs_spade_modulate_launch(long planes, long hw, const float *x, const float
 int sahs_spade_modulate_backward_launch(long planes, long hw, const float *x, const float *gamma, const float *out, const float *stats,
                                         const float *grad, float eps, float slope, float *dx, float *dgamma, float *dbeta, float *work,
                                         hipStream_t stream);
+int sahs_spade_modulate_bf16_launch(long planes, long hw, const unsigned short *x, const unsigned short *gamma, const unsigned short *beta,
+                                    float eps, float slope, unsigned short *out, float *stats, hipStream_t stream);
+int sahs_spade_modulate_backward_bf16_launch(long planes, long hw, const unsigned short *x, const unsigned short *gamma,
+                                             const unsigned short *out, const float *stats, const unsigned short *grad, float eps, float slope,
+                                             unsigned short *dx, unsigned short *dgamma, unsigned short *dbeta, float *work,
+                                             hipStream_t stream);
 // optim.hip (w1 = 1 - beta1, w2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): formed in double by the caller)
 int sahs_adam_step_launch(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float w1, float beta2, float w2,
                           float step_size, float bc2_sqrt, float eps, float grad_scale, hipStream_t stream);

@@ -213,6 +213,176 @@ __global__ void __launch_bounds__(256) spade_backward_apply_kernel(long hw, cons
     }
 }
 
+// ---- bf16 I/O forms of the four kernels above (the refiner under torch.autocast: the convolutions hand over bf16 tensors) ----
+// Every tensor operand is bf16 (bit patterns in unsigned short); the stats / work workspaces stay fp32 with the layout above.  All
+// arithmetic is the fp32 kernels': operands are widened on load (exact), the chunk sums, mean, variance, rstd, m0 and m1 are formed as
+// above, and each result is rounded to bf16 ONCE, on store (round to nearest even).  Traffic halves: 2 B read for the statistics + 6 B
+// read + 2 B written = 10 B per element forward, 8 B read per pass + 6 B written = 22 B backward.  W = 8: one 16-byte access (8 bf16)
+// per operand and thread, for hw % 8 == 0 and 16-byte aligned pointers; W = 1: element by element.  One loop body serves both.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float bf16_widen(unsigned bits) { return __builtin_bit_cast(float, bits << 16); }
+__device__ __forceinline__ unsigned bf16_round(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }      // as pack.hip: f32_to_bf16_rne
+
+// group i (W elements) of a plane that starts at p
+template <int W>
+__device__ __forceinline__ void bf16_load(const unsigned short *p, long i, float (&v)[W])
+{
+    if constexpr (W == 8) {
+        const u32x4 q = reinterpret_cast<const u32x4 *>(p)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[2 * k] = __builtin_bit_cast(float, q[k] << 16);
+            v[2 * k + 1] = __builtin_bit_cast(float, q[k] & 0xffff0000u);
+        }
+    } else {
+        v[0] = bf16_widen(p[i]);
+    }
+}
+template <int W>
+__device__ __forceinline__ void bf16_store(unsigned short *p, long i, const float (&v)[W])
+{
+    if constexpr (W == 8) {
+        u32x4 q;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = bf16_round(v[2 * k]) | bf16_round(v[2 * k + 1]) << 16;
+        reinterpret_cast<u32x4 *>(p)[i] = q;
+    } else {
+        p[i] = (unsigned short)bf16_round(v[0]);
+    }
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) instance_stats_bf16_kernel(long hw, const unsigned short *__restrict__ x, float *__restrict__ part, int pass)
+{
+    __shared__ float red[4];
+    const long plane = blockIdx.y;
+    const unsigned short *p = x + plane * hw;
+    float *pp = part + plane * (2 * SPADE_CHUNKS);
+    const long n = hw / W, per = (n + SPADE_CHUNKS - 1) / SPADE_CHUNKS;
+    const long lo = blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    const float mean = pass ? plane_mean(pp, hw) : 0.0f;
+    float s = 0.0f;
+    for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        float q[W];
+        bf16_load<W>(p, i, q);
+        if (pass) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) { const float d = q[k] - mean; s += d * d; }
+        } else if constexpr (W == 8) {
+            s += ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+        } else {
+            s += q[0];
+        }
+    }
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) pp[2 * blockIdx.x + pass] = s;
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) spade_modulate_bf16_kernel(long hw, const unsigned short *__restrict__ x,
+                                                                  const unsigned short *__restrict__ gamma,
+                                                                  const unsigned short *__restrict__ beta, const float *__restrict__ stats,
+                                                                  float eps, float slope, unsigned short *__restrict__ out)
+{
+    const long plane = blockIdx.y, base = plane * hw, n = hw / W;
+    float mean, rstd;
+    plane_norm(stats + plane * (2 * SPADE_CHUNKS), hw, eps, mean, rstd);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float xv[W], gv[W], bv[W], o[W];
+        bf16_load<W>(x + base, i, xv);
+        bf16_load<W>(gamma + base, i, gv);
+        bf16_load<W>(beta + base, i, bv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const float v = ((xv[k] - mean) * rstd) * (1.0f + gv[k]) + bv[k];
+            o[k] = v > 0.0f ? v : v * slope;
+        }
+        bf16_store<W>(out + base, i, o);
+    }
+}
+
+// the mask is read from the stored bf16 output (rounding keeps the sign: out > 0 exactly when the fp32 pre-activation was)
+template <int W>
+__global__ void __launch_bounds__(256) spade_backward_sums_bf16_kernel(long hw, const unsigned short *__restrict__ x,
+                                                                       const unsigned short *__restrict__ gamma,
+                                                                       const unsigned short *__restrict__ out, const float *__restrict__ stats,
+                                                                       const unsigned short *__restrict__ grad, float eps, float slope,
+                                                                       float *__restrict__ work)
+{
+    __shared__ float red[4];
+    const long plane = blockIdx.y, base = plane * hw;
+    float mean, rstd;
+    plane_norm(stats + plane * (2 * SPADE_CHUNKS), hw, eps, mean, rstd);
+    const long n = hw / W, per = (n + SPADE_CHUNKS - 1) / SPADE_CHUNKS;
+    const long lo = blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    float s0 = 0.0f, s1 = 0.0f;
+    for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        float gv[W], xv[W], mv[W], ov[W];
+        bf16_load<W>(grad + base, i, gv);
+        bf16_load<W>(x + base, i, xv);
+        bf16_load<W>(gamma + base, i, mv);
+        if (out) bf16_load<W>(out + base, i, ov);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const float dxh = ((!out || ov[k] > 0.0f) ? gv[k] : gv[k] * slope) * (1.0f + mv[k]);
+            s0 += dxh;
+            s1 += dxh * ((xv[k] - mean) * rstd);
+        }
+    }
+    s0 = block_sum256(s0, red);
+    s1 = block_sum256(s1, red);
+    if (threadIdx.x == 0) {
+        float *wp = work + plane * (2 * SPADE_CHUNKS) + 2 * blockIdx.x;
+        wp[0] = s0;
+        wp[1] = s1;
+    }
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) spade_backward_apply_bf16_kernel(long hw, const unsigned short *__restrict__ x,
+                                                                        const unsigned short *__restrict__ gamma,
+                                                                        const unsigned short *__restrict__ out, const float *__restrict__ stats,
+                                                                        const unsigned short *__restrict__ grad, const float *__restrict__ work,
+                                                                        float eps, float slope, unsigned short *__restrict__ dx,
+                                                                        unsigned short *__restrict__ dgamma, unsigned short *__restrict__ dbeta)
+{
+    const long plane = blockIdx.y, base = plane * hw, n = hw / W;
+    float mean, rstd;
+    plane_norm(stats + plane * (2 * SPADE_CHUNKS), hw, eps, mean, rstd);
+    float m0 = 0.0f, m1 = 0.0f;
+    if (dx) {
+        const float *wp = work + plane * (2 * SPADE_CHUNKS);
+#pragma unroll
+        for (int c = 0; c < SPADE_CHUNKS; ++c) { m0 += wp[2 * c]; m1 += wp[2 * c + 1]; }
+        m0 /= (float)hw;
+        m1 /= (float)hw;
+    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float gv[W], xv[W], ov[W], mv[W], dy[W], xh[W], o[W];
+        bf16_load<W>(grad + base, i, gv);
+        bf16_load<W>(x + base, i, xv);
+        if (out) bf16_load<W>(out + base, i, ov);
+        if (dx) bf16_load<W>(gamma + base, i, mv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            dy[k] = (!out || ov[k] > 0.0f) ? gv[k] : gv[k] * slope;
+            xh[k] = (xv[k] - mean) * rstd;
+        }
+        if (dbeta) bf16_store<W>(dbeta + base, i, dy);
+        if (dgamma) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) o[k] = dy[k] * xh[k];
+            bf16_store<W>(dgamma + base, i, o);
+        }
+        if (dx) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) o[k] = rstd * ((dy[k] * (1.0f + mv[k]) - m0) - xh[k] * m1);
+            bf16_store<W>(dx + base, i, o);
+        }
+    }
+}
+
 }  // namespace sahs
 
 // the modulate-shaped grid: a 256-thread workgroup per 256 elements (or vectors) of a plane, capped at ~8 k workgroups in all
@@ -261,5 +431,45 @@ extern "C" int sahs_spade_modulate_launch(long planes, long hw, const float *x, 
     const dim3 grid = spade_plane_grid(vec ? hw / 4 : hw, planes);
     if (vec) sahs::spade_modulate_kernel<true><<<grid, 256, 0, stream>>>(hw, x, gamma, beta, stats, eps, slope, out);
     else sahs::spade_modulate_kernel<false><<<grid, 256, 0, stream>>>(hw, x, gamma, beta, stats, eps, slope, out);
+    return (int)hipGetLastError();
+}
+
+// ---- the bf16 forms: same launches, same grids, groups of 8 elements where the fp32 forms take 4 ----
+extern "C" int sahs_spade_modulate_bf16_launch(long planes, long hw, const unsigned short *x, const unsigned short *gamma,
+                                               const unsigned short *beta, float eps, float slope, unsigned short *out, float *stats,
+                                               hipStream_t stream)
+{
+    if (planes <= 0 || hw <= 0) return 0;
+    if (planes > 65535) return -2;      // gridDim.y (capi.hip refuses it by name first)
+    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    const bool vec = (hw % 8 == 0) && al(x) && al(gamma) && al(beta) && al(out);
+    const dim3 sgrid(sahs::SPADE_CHUNKS, (unsigned)planes);
+    for (int pass = 0; pass < 2; ++pass) {
+        if (vec) sahs::instance_stats_bf16_kernel<8><<<sgrid, 256, 0, stream>>>(hw, x, stats, pass);
+        else sahs::instance_stats_bf16_kernel<1><<<sgrid, 256, 0, stream>>>(hw, x, stats, pass);
+    }
+    const dim3 grid = spade_plane_grid(vec ? hw / 8 : hw, planes);
+    if (vec) sahs::spade_modulate_bf16_kernel<8><<<grid, 256, 0, stream>>>(hw, x, gamma, beta, stats, eps, slope, out);
+    else sahs::spade_modulate_bf16_kernel<1><<<grid, 256, 0, stream>>>(hw, x, gamma, beta, stats, eps, slope, out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int sahs_spade_modulate_backward_bf16_launch(long planes, long hw, const unsigned short *x, const unsigned short *gamma,
+                                                        const unsigned short *out, const float *stats, const unsigned short *grad, float eps,
+                                                        float slope, unsigned short *dx, unsigned short *dgamma, unsigned short *dbeta,
+                                                        float *work, hipStream_t stream)
+{
+    if (planes <= 0 || hw <= 0) return 0;
+    if (planes > 65535) return -2;      // gridDim.y
+    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };      // (a null pointer is never dereferenced)
+    const bool vec = (hw % 8 == 0) && al(x) && al(gamma) && al(out) && al(grad) && al(dx) && al(dgamma) && al(dbeta);
+    if (dx) {
+        const dim3 sgrid(sahs::SPADE_CHUNKS, (unsigned)planes);
+        if (vec) sahs::spade_backward_sums_bf16_kernel<8><<<sgrid, 256, 0, stream>>>(hw, x, gamma, out, stats, grad, eps, slope, work);
+        else sahs::spade_backward_sums_bf16_kernel<1><<<sgrid, 256, 0, stream>>>(hw, x, gamma, out, stats, grad, eps, slope, work);
+    }
+    const dim3 grid = spade_plane_grid(vec ? hw / 8 : hw, planes);
+    if (vec) sahs::spade_backward_apply_bf16_kernel<8><<<grid, 256, 0, stream>>>(hw, x, gamma, out, stats, grad, work, eps, slope, dx, dgamma, dbeta);
+    else sahs::spade_backward_apply_bf16_kernel<1><<<grid, 256, 0, stream>>>(hw, x, gamma, out, stats, grad, work, eps, slope, dx, dgamma, dbeta);
     return (int)hipGetLastError();
 }

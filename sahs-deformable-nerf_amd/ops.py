@@ -356,22 +356,39 @@ def render_rays_rows(packed, frame, rays, num_coarse, num_fine, rows, precision=
     return rows
 
 
+def _spade_entry(dtype, backward=False):
+    """The fp32 or the bf16 entry point of the fused modulation (include/sahs_nerf.h) -> (function, its name)."""
+    name = "sahs_spade_modulate" + ("_backward" if backward else "") + ("_bf16" if dtype == torch.bfloat16 else "")
+    return getattr(_lib.lib(), name), name
+
+
 def _spade_modulate_forward(x, gamma, beta, eps, slope):
-    """-> (x, gamma as the kernel read them (contiguous), out, the statistics workspace the launch left)."""
-    x, gamma, beta = _req(x, "x"), _req(gamma, "gamma"), _req(beta, "beta")
+    """x, gamma, beta of ONE dtype, float32 or bfloat16 (spade_modulate sees to it)
+    -> (x, gamma as the kernel read them (contiguous), out, the statistics workspace the launch left)."""
+    dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16 else torch.float32
+    x, gamma, beta = _req(x, "x", dtype), _req(gamma, "gamma", dtype), _req(beta, "beta", dtype)
     if x.dim() != 4 or gamma.shape != x.shape or beta.shape != x.shape:
         raise _lib.SahsError("spade_modulate: x, gamma, beta must be NCHW tensors of one shape, got %s %s %s" % (tuple(x.shape), tuple(gamma.shape), tuple(beta.shape)))
     planes, hw = x.shape[0] * x.shape[1], x.shape[2] * x.shape[3]
     out = torch.empty_like(x)
     stats = torch.empty(int(_lib.lib().sahs_spade_modulate_workspace_words(planes)), dtype=torch.float32, device=x.device)
-    check(_lib.lib().sahs_spade_modulate(planes, hw, _p(x), _p(gamma), _p(beta), float(eps), float(slope), _p(out), _p(stats), _stream()), "sahs_spade_modulate")
+    f, name = _spade_entry(dtype)
+    check(f(planes, hw, _p(x), _p(gamma), _p(beta), float(eps), float(slope), _p(out), _p(stats), _stream()), name)
     return x, gamma, out, stats
 
 
 def spade_modulate(x, gamma, beta, eps=1e-5, slope=1.0):
     """lrelu_slope(InstanceNorm2d(x) * (1 + gamma) + beta) for NCHW tensors of one shape, fused (include/sahs_nerf.h: sahs_spade_modulate).
     Differentiable (SpadeModulateFn: sahs_spade_modulate_backward) when grad mode is on and one of the three tensors requires a gradient;
-    with plain tensors it is the two launches of the forward alone, whatever the grad mode."""
+    with plain tensors it is the two launches of the forward alone, whatever the grad mode.
+    dtype: three float32 tensors take the fp32 kernels; three bfloat16 tensors (what the convolutions hand over under
+    torch.autocast) take the bf16 kernels -- fp32 arithmetic, bf16 output and gradients (sahs_spade_modulate_bf16); a mixture of the two
+    is widened with .float() and takes the fp32 kernels, torch's own promotion rule.  Any other dtype is refused."""
+    dtypes = [t.dtype for t in (x, gamma, beta) if isinstance(t, torch.Tensor)]
+    if any(d not in (torch.float32, torch.bfloat16) for d in dtypes):
+        raise _lib.SahsError("spade_modulate: x, gamma, beta must be torch.float32 or torch.bfloat16, got %s" % ", ".join(str(d) for d in dtypes))
+    if len(set(dtypes)) > 1:
+        x, gamma, beta = (t.float() if isinstance(t, torch.Tensor) else t for t in (x, gamma, beta))
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, gamma, beta)):
         return SpadeModulateFn.apply(x, gamma, beta, float(eps), float(slope))
     return _spade_modulate_forward(x, gamma, beta, eps, slope)[2]
@@ -711,7 +728,8 @@ class SpadeModulateFn(torch.autograd.Function):
     """spade_modulate as a differentiable op (Stage-II refiner training): the forward's two launches, and a two-launch fused backward
     (include/sahs_nerf.h: sahs_spade_modulate_backward) in place of the six autograd nodes of the written-out formula.  Saved: x, gamma,
     the output -- the activation mask is read from it -- and the forward's statistics workspace; beta is not needed.  Gradients are
-    formed only for the inputs that ask for one.  Not twice differentiable."""
+    formed only for the inputs that ask for one.  Not twice differentiable.  bfloat16 tensors: x, gamma and the output are saved as
+    bf16 (half the bytes), the backward is sahs_spade_modulate_backward_bf16, and grad_out must come in the dtype of the saved x."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, slope):
@@ -726,7 +744,7 @@ class SpadeModulateFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         s = _load_named(ctx)
-        grad_out = _req(grad_out, "grad_out")      # (contiguous: out.sum().backward() hands over a stride-0 expansion)
+        grad_out = _req(grad_out, "grad_out", s.x.dtype)      # (contiguous: out.sum().backward() hands over a stride-0 expansion)
         if grad_out.shape != s.x.shape:
             raise _lib.SahsError("SpadeModulateFn.backward: gradient of shape %s for an output of shape %s" % (tuple(grad_out.shape), tuple(s.x.shape)))
         planes, hw = s.x.shape[0] * s.x.shape[1], s.x.shape[2] * s.x.shape[3]
@@ -734,9 +752,9 @@ class SpadeModulateFn(torch.autograd.Function):
         work = None
         if dx is not None:
             work = torch.empty(int(_lib.lib().sahs_spade_modulate_backward_workspace_words(planes)), dtype=torch.float32, device=s.x.device)
-        check(_lib.lib().sahs_spade_modulate_backward(planes, hw, _p(s.x), _p(s.gamma), _p(s.out), _p(s.stats), _p(grad_out), float(ctx.eps),
-                                                      float(ctx.slope), _p(dx), _p(dgamma), _p(dbeta), _p(work), _stream()),
-              "sahs_spade_modulate_backward")
+        f, name = _spade_entry(s.x.dtype, backward=True)
+        check(f(planes, hw, _p(s.x), _p(s.gamma), _p(s.out), _p(s.stats), _p(grad_out), float(ctx.eps), float(ctx.slope), _p(dx), _p(dgamma),
+                _p(dbeta), _p(work), _stream()), name)
         return dx, dgamma, dbeta, None, None
 
 

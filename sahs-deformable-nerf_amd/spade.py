@@ -9,6 +9,8 @@ two-launch backward in place of six autograd nodes per SPADE layer -- so the gen
 reference's train_get_texture_photo.py / train_get_texture_photo_audio.py (clamp, MSE, Adam; the discriminator and the VGG loss that
 _init_spade.py also defines are never called by those loops and are not built).
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -227,14 +229,21 @@ def refine_learning_rate(cfg, epoch):
     return t.lr_G / t.epochs_decay * (t.epochs + t.epochs_decay - epoch)
 
 
-def refine_step(G, optimizer, I_src, I_raw, target, driving=None):
+def refine_step(G, optimizer, I_src, I_raw, target, driving=None, autocast_dtype=None):
     """One training step of the Stage-II generator, train_get_texture_photo.py:168-179 (``driving`` = the audio window of
     train_get_texture_photo_audio.py:143-192 for Generator_audio): MSE between the clamped output and the target frame, backward,
     optimiser step.  Returns the loss (a 0-d tensor; no synchronisation here).  The caller does ``G.train()``, the data loading and the
-    learning-rate schedule, as with training.train_step."""
+    learning-rate schedule, as with training.train_step.
+    autocast_dtype=torch.bfloat16 (not in the reference): the generator's forward and the loss run under
+    ``torch.autocast("cuda", dtype=torch.bfloat16)`` -- the convolutions on the bf16 matrix pipe, the SPADE modulation on its bf16
+    kernels -- while backward() and the optimiser step run outside it; the parameters and Adam's state stay fp32, and bf16 has fp32's
+    exponent range, so there is no GradScaler."""
+    if autocast_dtype not in (None, torch.bfloat16):
+        raise ValueError("refine_step: autocast_dtype must be None or torch.bfloat16, got %r" % (autocast_dtype,))
     optimizer.zero_grad()
-    fake = G(I_src, I_raw) if driving is None else G(I_src, I_raw, driving)
-    loss = F.mse_loss(fake.clamp(0, 1), target)
+    with contextlib.nullcontext() if autocast_dtype is None else torch.autocast("cuda", dtype=autocast_dtype):
+        fake = G(I_src, I_raw) if driving is None else G(I_src, I_raw, driving)
+        loss = F.mse_loss(fake.clamp(0, 1), target)
     loss.backward()
     optimizer.step()
     return loss.detach()

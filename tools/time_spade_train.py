@@ -10,6 +10,16 @@ element-wise torch ops in its place) alternated round by round:
   * the op's backward alone on (1, 64, size / 2, size / 2) -- the largest SPADE layer of the network -- through the C ABI with preallocated
     buffers, HIP events around 200 launch pairs, against its algorithmic 44 B per element (16 read by the sums pass, 16 read + 12
     written by the apply pass); beside it the swapped backward of the same tensors (autograd of the six ops), for scale.
+
+  python tools/time_spade_train.py --autocast bf16 [--size 512] [...] [--out profiles/spade_bf16_step.json]
+
+The refiner under ``torch.autocast("cuda", dtype=torch.bfloat16)`` (profiles/spade_bf16_step.json).  Three variants, alternated round by
+round in one process: fp32 with the fused op; autocast with the fused bf16 op (``refine_step(..., autocast_dtype=torch.bfloat16)``);
+autocast with the op swapped for the six torch ops.  For each: the training step and its peak memory as above, ``Generator`` inference
+(eval() under no_grad) in ms per image, and the op alone on (1, 64, size / 2, size / 2), forward and backward, by HIP events -- fp32 and
+bf16 through the C ABI (20 / 44 and 10 / 22 B per element), and the six ops on bf16 tensors for scale.  The file records whether autocast
+with the fused op is not slower than autocast with the swapped op, and the bf16 op not slower than the fp32 op, each beyond the run's
+own min-max spread; nothing is tuned to make them hold.
 There is no CPU path: without a GPU this fails.
 """
 import argparse
@@ -35,22 +45,132 @@ def six_ops(x, gamma, beta, eps=1e-5, slope=1.0):
     return F.leaky_relu(F.instance_norm(x, eps=eps) * (1 + gamma) + beta, slope)
 
 
-def steps_ms(G, opt, inputs, steps):
+def steps_ms(G, opt, inputs, steps, **kw):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss = spade.refine_step(G, opt, *inputs)
+        loss = spade.refine_step(G, opt, *inputs, **kw)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps * 1e3, float(loss)
 
 
-def step_peak_bytes(G, opt, inputs):
+def step_peak_bytes(G, opt, inputs, **kw):
     torch.cuda.synchronize()
     base = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
-    spade.refine_step(G, opt, *inputs)
+    spade.refine_step(G, opt, *inputs, **kw)
     torch.cuda.synchronize()
     return torch.cuda.max_memory_allocated() - base
+
+
+def inference_ms(G, inputs, steps, autocast):
+    """eval() under no_grad: ms per image, a host clock around ``steps`` forwards that end in a device synchronise."""
+    G.eval()
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+        for _ in range(2):
+            G(*inputs)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            G(*inputs)
+        torch.cuda.synchronize()
+    G.train()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def not_slower(a, b):
+    """a, b: the rounds' timings of two variants of one run.  a counts as slower only beyond the run's own min-max spread: when even its
+    fastest round is slower than b's slowest."""
+    return not min(a) > max(b)
+
+
+def main_autocast(args):
+    """--autocast bf16: fp32 fused, autocast with the fused bf16 op, autocast with the op swapped for the six-op formula (module
+    docstring), alternated round by round in one process -> profiles/spade_bf16_step.json."""
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(1)
+    torch.manual_seed(1)
+    #           (the op, refine_step's autocast_dtype)
+    variants = {"fp32_fused": (FUSED, None), "autocast_fused": (FUSED, torch.bfloat16), "autocast_swapped": (six_ops, torch.bfloat16)}
+    first = spade.Generator().to(dev).train()
+    nets = {k: (first if i == 0 else copy.deepcopy(first)) for i, k in enumerate(variants)}
+    opts = {k: torch.optim.Adam(G.parameters(), lr=2e-4, betas=(0.5, 0.999)) for k, G in nets.items()}
+    inputs = tuple(torch.rand(1, 3, args.size, args.size, device=dev, generator=gen) for _ in range(3))
+    res = {k: {"train_ms_per_step": [], "train_peak_bytes_above_resident": [], "inference_ms_per_image": []} for k in variants}
+    for k, (op, dt) in variants.items():      # warm-up: MIOpen picks its algorithms (per dtype), Adam allocates its state
+        ops.spade_modulate = op
+        t0 = time.perf_counter()
+        res[k]["first_loss"] = steps_ms(nets[k], opts[k], inputs, args.warmup, autocast_dtype=dt)[1]
+        res[k]["warmup_wall_s"] = time.perf_counter() - t0
+        inference_ms(nets[k], inputs[:2], 1, dt is not None)
+    for _ in range(args.rounds):
+        for k, (op, dt) in variants.items():
+            ops.spade_modulate = op
+            res[k]["train_ms_per_step"].append(steps_ms(nets[k], opts[k], inputs, args.steps, autocast_dtype=dt)[0])
+            res[k]["train_peak_bytes_above_resident"].append(step_peak_bytes(nets[k], opts[k], inputs, autocast_dtype=dt))
+            res[k]["inference_ms_per_image"].append(inference_ms(nets[k], inputs[:2], args.steps, dt is not None))
+    ops.spade_modulate = FUSED
+    for k in variants:
+        res[k]["train_ms_per_step_best"] = min(res[k]["train_ms_per_step"])
+        res[k]["inference_ms_per_image_best"] = min(res[k]["inference_ms_per_image"])
+    # the op alone, forward and backward, through the C ABI on preallocated buffers
+    C, H = 64, args.size // 2
+    L, P, st = _lib.lib(), ops._p, ops._stream()
+    src = [torch.randn(1, C, H, H, device=dev, generator=gen) for _ in range(4)]
+    op = {}
+    calls = {}
+    for tag, dtype, suffix in (("fp32", torch.float32, ""), ("bf16", torch.bfloat16, "_bf16")):
+        x, gamma, beta, g = (t.to(dtype) for t in src)
+        out, dx, dgamma, dbeta = (torch.empty_like(x) for _ in range(4))
+        stats = torch.empty(int(L.sahs_spade_modulate_workspace_words(C)), device=dev)
+        work = torch.empty(int(L.sahs_spade_modulate_backward_workspace_words(C)), device=dev)
+        fwd_f, bwd_f = getattr(L, "sahs_spade_modulate" + suffix), getattr(L, "sahs_spade_modulate_backward" + suffix)
+        keep = (x, gamma, beta, g, out, dx, dgamma, dbeta, stats, work)
+        fwd = lambda f=fwd_f, t=keep: _lib.check(f(C, H * H, P(t[0]), P(t[1]), P(t[2]), 1e-5, 0.2, P(t[4]), P(t[8]), st), "forward")
+        bwd = lambda f=bwd_f, t=keep: _lib.check(f(C, H * H, P(t[0]), P(t[1]), P(t[4]), P(t[8]), P(t[3]), 1e-5, 0.2, P(t[5]), P(t[6]), P(t[7]),
+                                                   P(t[9]), st), "backward")
+        fwd()
+        calls[tag] = (fwd, bwd)
+        op[tag] = {"forward_ms": [], "backward_ms": []}
+    xb, gb, bb, gg = (t.bfloat16() for t in src)
+    leaves = [t.clone().requires_grad_(True) for t in (xb, gb, bb)]
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        y = six_ops(*leaves, slope=0.2)
+
+    def swapped_fwd():
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            six_ops(xb, gb, bb, slope=0.2)
+
+    calls["swapped_bf16"] = (swapped_fwd, lambda: torch.autograd.grad(y, leaves, gg.to(y.dtype), retain_graph=True))
+    op["swapped_bf16"] = {"forward_ms": [], "backward_ms": []}
+    for _ in range(args.rounds):
+        for tag, (fwd, bwd) in calls.items():
+            reps = 50 if tag == "swapped_bf16" else 200
+            op[tag]["forward_ms"].append(events_ms(fwd, reps))
+            op[tag]["backward_ms"].append(events_ms(bwd, reps))
+    n = C * H * H
+    for tag, per in (("fp32", (20, 44)), ("bf16", (10, 22))):
+        op[tag].update(bytes_per_element_forward=per[0], bytes_per_element_backward=per[1],
+                       forward_GB_per_s=per[0] * n / min(op[tag]["forward_ms"]) / 1e6, backward_GB_per_s=per[1] * n / min(op[tag]["backward_ms"]) / 1e6)
+    op.update(shape=[1, C, H, H], timing="HIP events on the launch stream: 200 C-ABI calls (two launches each) on preallocated buffers per round; "
+              "swapped_bf16 = 50 calls of the six torch ops on bf16 tensors under autocast (forward under no_grad; backward = "
+              "torch.autograd.grad through their graph), allocations and launch pacing included",
+              note="the tensors of one call fit the 256 MB last-level cache: the rates are not HBM rates")
+    checks = {"autocast_fused_step_not_slower_than_autocast_swapped": not_slower(res["autocast_fused"]["train_ms_per_step"], res["autocast_swapped"]["train_ms_per_step"]),
+              "autocast_fused_inference_not_slower_than_autocast_swapped": not_slower(res["autocast_fused"]["inference_ms_per_image"], res["autocast_swapped"]["inference_ms_per_image"]),
+              "bf16_op_forward_not_slower_than_fp32": not_slower(op["bf16"]["forward_ms"], op["fp32"]["forward_ms"]),
+              "bf16_op_backward_not_slower_than_fp32": not_slower(op["bf16"]["backward_ms"], op["fp32"]["backward_ms"]),
+              "rule": "a is slower than b only if min(a's rounds) > max(b's rounds): beyond the run's own min-max spread"}
+    result = {"command": "python tools/time_spade_train.py --autocast bf16 --size %d --steps %d --warmup %d --rounds %d" % (args.size, args.steps, args.warmup, args.rounds),
+              "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
+              "workload": "Generator: refine_step in train() mode (forward, clamp, MSE, backward, Adam) and eval() inference under no_grad on a %dx%d "
+                          "frame; convolutions on MIOpen in every variant; parameters and Adam state fp32 in every variant" % (args.size, args.size),
+              "steps_per_window": args.steps, "rounds": args.rounds, "variants": res, "op": op, "checks": checks}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
 
 
 def events_ms(fn, reps):
@@ -71,10 +191,15 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "spade_train_step.json"))
+    ap.add_argument("--autocast", choices=("bf16",), default=None)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "spade_bf16_step.json" if args.autocast else "spade_train_step.json")
     if not torch.cuda.is_available():
         raise SystemExit("time_spade_train.py needs a GPU: nothing here can be measured on a CPU")
+    if args.autocast:
+        return main_autocast(args)
     dev = torch.device("cuda:0")
     gen = torch.Generator(device=dev).manual_seed(1)
     torch.manual_seed(1)
