@@ -2,8 +2,11 @@
 reference's ``nerf/_init_spade.py`` (:114-160, :235-282) with the reference's ``state_dict`` layout (including the duplicated
 ``conv1`` / ``conv1_sn`` entries: the reference registers each spectral-normalised convolution under two names), so its checkpoints load.
 
-What runs where: the 3x3 convolutions are library work -- ``torch.nn.functional.conv2d`` is MIOpen on ROCm -- and
-a hand-written convolution would buy nothing here; the normalise / modulate / activate chain between them, which the reference runs as
+What runs where (DESIGN.md sections 8, 9): the 3x3 convolutions are library work -- ``torch.nn.functional.conv2d`` is MIOpen on ROCm --
+forward and backward, in fp32 and under bf16 autocast.  That was judged for the fp32 forward and has since been measured for the bf16
+backward: of the 231 ms autocast training step the GPU works 29 ms, the library's bf16 convolution backward is faster than its fp32
+one, and MFMA kernels written for it were 2 ms per step slower than the library's (the step's 200 ms are host time of spectral norm's
+bf16 matrix-vector products: section 9).  The normalise / modulate / activate chain between them, which the reference runs as
 six elementwise passes, is ONE fused HIP kernel behind a statistics pass (``ops.spade_modulate``).  It is differentiable -- a fused
 two-launch backward in place of six autograd nodes per SPADE layer -- so the generators train: ``refine_step`` is the step of the
 reference's train_get_texture_photo.py / train_get_texture_photo_audio.py (clamp, MSE, Adam; the discriminator and the VGG loss that

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Condense gpurun_out/prof_<round> (tools/profile.sh <round>) into the tracked summaries under profiles/ (legs that were not run are skipped): per-kernel statistics of the fp32
 headline, the bf16 / bf16x3 / NeRFace mixed-precision legs and the training step, the PMC summary of the field kernels' dominant
-dispatches (+ the small JSON that bench.py quotes as roofline.traffic), and the per-kernel HBM traffic of the training step."""
+dispatches (+ the small JSON that bench.py quotes as roofline.traffic), and the per-kernel HBM traffic of the training step.
+
+  summarize_profiles.py --steady <kernel_trace.csv> <marker kernel> <markers to skip> <output csv> <header>
+one kernel trace alone -> per-kernel statistics of the dispatches behind the skip-th marker dispatch (steady_kernel_stats)."""
 import collections
 import csv
 import glob
@@ -63,6 +66,31 @@ def kind(kn, leg):
         return ("nf_f32_" if nf else ("x3leg_f32_" if leg == "bf16x3" else "f32_")) + lab
     return None
 
+
+def steady_kernel_stats(trace_csv, marker, skip, dst, header):
+    """Per-kernel statistics of the STEADY part of a ``rocprofv3 --kernel-trace`` run, in the layout of kernel_stats(): only the
+    dispatches that start after the skip-th dispatch of a marker kernel count (the program launches the marker after every step), so
+    the library's first-call algorithm search -- which dwarfs the steps themselves -- is left out.  The marker is not counted."""
+    rows = sorted(csv.DictReader(open(trace_csv)), key=lambda r: int(r["Start_Timestamp"]))
+    marks = [int(r["Start_Timestamp"]) for r in rows if marker in r["Kernel_Name"]]
+    t0, steps = marks[skip - 1], len(marks) - skip
+    agg = collections.OrderedDict()
+    for r in rows:
+        if int(r["Start_Timestamp"]) > t0 and marker not in r["Kernel_Name"]:
+            agg.setdefault(r["Kernel_Name"], []).append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+    total = sum(sum(v) for v in agg.values())
+    with open(dst, "w") as f:
+        f.write("# %s\n# steady part: the %d steps after marker %d of %d (%s); kernel time %.3f ms per step\n" % (header, steps, skip, len(marks), marker, total / steps / 1e6))
+        w = csv.writer(f)
+        w.writerow(["Name", "Calls", "TotalDurationNs", "AverageNs", "Percentage", "MinNs", "MaxNs"])
+        for name, v in sorted(agg.items(), key=lambda kv: -sum(kv[1])):
+            w.writerow([short(name), len(v), sum(v), "%.1f" % (sum(v) / len(v)), "%.2f" % (100.0 * sum(v) / total), min(v), max(v)])
+    return total / steps / 1e6
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--steady":      # --steady <kernel_trace.csv> <marker kernel> <markers to skip> <output csv> <header>
+    print("%.3f ms of kernel time per steady step" % steady_kernel_stats(sys.argv[2], sys.argv[3], int(sys.argv[4]), sys.argv[5], sys.argv[6]))
+    sys.exit(0)
 
 stats = {}
 for leg, args, steps, what in (("f32", "--precision fp32", 8, "fp32 W512 headline; per 131,072-ray chunk: field<false,0> = coarse launch (8.39 M samples, whole network), "
