@@ -397,6 +397,35 @@ int sahs_spade_modulate_backward_bf16(long planes, long hw, const unsigned short
                                       const float *stats, const unsigned short *grad_out, float eps, float slope, unsigned short *dx,
                                       unsigned short *dgamma, unsigned short *dbeta, float *work, void *stream);
 
+/* ---- Stage-II refiner training: spectral norm of a table of weights, fused ----
+ * torch.nn.utils.spectral_norm's SpectralNorm.compute_weight (dim 0, n_power_iterations 1) for up to SAHS_SPECTRAL_NORM_MAX_JOBS weights
+ * of mixed shapes per call.  Job k is a weight viewed as a contiguous row-major h[k] x w[k] fp32 matrix W (h = out channels,
+ * w = in * kh * kw) with its vectors u (h) and v (w).  W, u, v, out, saved, grad_out, dW are HOST arrays of `jobs` device pointers,
+ * h and w host arrays of ints; they are read before the call returns and travel to the kernels as arguments (no device-side table, no
+ * allocation, no synchronisation).
+ *   power_iteration = 1 (training):  t = W^T u,  v <- t / max(|t|_2, eps);   s = W v,  u <- s / max(|s|_2, eps);   sigma = u . s
+ *   power_iteration = 0 (eval):      u, v are read only,  sigma = u . (W v)
+ *   out = W / sigma
+ * With power_iteration = 1 the job's u and v are updated IN PLACE (they are the module's buffers).  The u, v and sigma that formed the
+ * output are also written to the job's saved area, h + w + 1 floats (u, then v, then sigma), which is what the backward reads -- so a
+ * second forward on the same u, v before the first one's backward disturbs nothing (torch clones them for that reason).  out_bf16 = 0:
+ * out holds floats; otherwise bf16 bit patterns, the fp32 quotient rounded once, to nearest even, on store.  All arithmetic is fp32.
+ * W = 0 gives sigma = 0 and a non-finite out, as in torch.
+ *   backward:  dW = G / sigma - (sum(G o W) / sigma^2) u v^T      (u, v constants of the graph, as in torch)
+ * G = grad_out = dL/d out, fp32 (grad_bf16 = 0) or bf16 bit patterns widened on load; W and saved as the forward read and left them;
+ * dW fp32.
+ * Launches, whatever `jobs`: forward two (u, v, sigma: one workgroup per job; then out = W / sigma over the chip), backward one (a
+ * workgroup per job).  Every sum has a fixed order and there are no atomics: results are bit-reproducible.  16-byte accesses where
+ * w % 4 == 0 (w % 8 == 0 for a bf16 out or grad_out) and the pointers -- W, out, grad_out, dW and saved + h -- are 16-byte aligned;
+ * element by element otherwise, job by job.
+ * Invalid, refused with a message that names it before anything is launched: jobs < 1 or > SAHS_SPECTRAL_NORM_MAX_JOBS; a null table
+ * or a null pointer in one; h < 1, w < 1 or h * w >= 2^31; eps <= 0; power_iteration other than 0 or 1. */
+#define SAHS_SPECTRAL_NORM_MAX_JOBS 32
+int sahs_spectral_norm_forward(int jobs, const float *const *W, float *const *u, float *const *v, void *const *out, float *const *saved,
+                               const int *h, const int *w, int out_bf16, int power_iteration, float eps, void *stream);
+int sahs_spectral_norm_backward(int jobs, const float *const *W, const float *const *saved, const void *const *grad_out, float *const *dW,
+                                const int *h, const int *w, int grad_bf16, void *stream);
+
 /* ---- launch probe (opt-in measurement aid; the one exception to "never synchronises") ----
  * While armed on the calling thread, every FIELD-kernel launch the library makes (from any entry point above) is bracketed by two HIP
  * events recorded on the launch stream, up to `capacity` launches (further ones are counted as dropped and run unprobed).

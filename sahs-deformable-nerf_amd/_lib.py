@@ -81,6 +81,8 @@ SIGNATURES = {
     "sahs_spade_modulate_backward": (_I, [_L, _L, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "sahs_spade_modulate_bf16": (_I, [_L, _L, _P, _P, _P, _F, _F, _P, _P, _P]),
     "sahs_spade_modulate_backward_bf16": (_I, [_L, _L, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "sahs_spectral_norm_forward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "sahs_spectral_norm_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "sahs_probe_arm": (_I, [_I]),
     "sahs_probe_disarm": (_I, []),
     "sahs_probe_count": (_I, []),

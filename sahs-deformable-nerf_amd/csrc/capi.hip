@@ -329,6 +329,43 @@ int sahs_spade_modulate_backward_bf16(long planes, long hw, const unsigned short
     return e ? hip_fail("sahs_spade_modulate_backward_bf16", e) : 0;
 }
 
+// the fused, batched spectral norm: the tables are host arrays of device pointers; every refusal names what it refuses
+static int spectral_norm_shapes(const char *who, int jobs, const int *h, const int *w)
+{
+    if (jobs < 1 || jobs > SAHS_SPECTRAL_NORM_MAX_JOBS)
+        return fail(1, "%s: jobs = %d, must be 1 .. %d (capi.hip:%d)", who, jobs, SAHS_SPECTRAL_NORM_MAX_JOBS, __LINE__);
+    if (!h || !w) return fail(1, "%s: null pointer for the table h or w (capi.hip:%d)", who, __LINE__);
+    for (int k = 0; k < jobs; ++k)
+        if (h[k] < 1 || w[k] < 1 || (long)h[k] * w[k] >= 2147483648L)
+            return fail(1, "%s: job %d is %d x %d, needs h >= 1, w >= 1, h * w < 2^31 (capi.hip:%d)", who, k, h[k], w[k], __LINE__);
+    return 0;
+}
+#define SN_TABLE(who, t) do { if (!(t)) return fail(1, "%s: null pointer for the table %s (capi.hip:%d)", who, #t, __LINE__); \
+    for (int k_ = 0; k_ < jobs; ++k_) if (!(t)[k_]) return fail(1, "%s: null pointer %s[%d] (capi.hip:%d)", who, #t, k_, __LINE__); } while (0)
+
+int sahs_spectral_norm_forward(int jobs, const float *const *W, float *const *u, float *const *v, void *const *out, float *const *saved,
+                               const int *h, const int *w, int out_bf16, int power_iteration, float eps, void *stream)
+{
+    const char *who = "sahs_spectral_norm_forward";
+    if (int e = spectral_norm_shapes(who, jobs, h, w)) return e;
+    SN_TABLE(who, W); SN_TABLE(who, u); SN_TABLE(who, v); SN_TABLE(who, out); SN_TABLE(who, saved);
+    if (!(eps > 0.0f)) return fail(1, "%s: eps = %g, must be > 0 (capi.hip:%d)", who, (double)eps, __LINE__);
+    if (power_iteration != 0 && power_iteration != 1)
+        return fail(1, "%s: power_iteration = %d, must be 0 (eval) or 1 (training) (capi.hip:%d)", who, power_iteration, __LINE__);
+    int e = sahs_spectral_norm_forward_launch(jobs, W, u, v, out, saved, h, w, out_bf16 != 0, power_iteration, eps, (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
+int sahs_spectral_norm_backward(int jobs, const float *const *W, const float *const *saved, const void *const *grad_out, float *const *dW,
+                                const int *h, const int *w, int grad_bf16, void *stream)
+{
+    const char *who = "sahs_spectral_norm_backward";
+    if (int e = spectral_norm_shapes(who, jobs, h, w)) return e;
+    SN_TABLE(who, W); SN_TABLE(who, saved); SN_TABLE(who, grad_out); SN_TABLE(who, dW);
+    int e = sahs_spectral_norm_backward_launch(jobs, W, saved, grad_out, dW, h, w, grad_bf16 != 0, (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
 int sahs_composite_forward_rows(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
                                 const float *bg, int white_background, float *weights, float *rows, int row_ld, int fine_pass, void *stream)
 {

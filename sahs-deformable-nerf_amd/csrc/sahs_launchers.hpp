@@ -67,6 +67,12 @@ int sahs_spade_modulate_backward_bf16_launch(long planes, long hw, const unsigne
                                              const unsigned short *out, const float *stats, const unsigned short *grad, float eps, float slope,
                                              unsigned short *dx, unsigned short *dgamma, unsigned short *dbeta, float *work,
                                              hipStream_t stream);
+// spectral_norm.hip (the tables as host arrays of device pointers, already validated: capi.hip)
+int sahs_spectral_norm_forward_launch(int jobs, const float *const *W, float *const *u, float *const *v, void *const *out,
+                                      float *const *saved, const int *h, const int *w, int out_bf16, int power_iteration, float eps,
+                                      hipStream_t stream);
+int sahs_spectral_norm_backward_launch(int jobs, const float *const *W, const float *const *saved, const void *const *grad_out,
+                                       float *const *dW, const int *h, const int *w, int grad_bf16, hipStream_t stream);
 // optim.hip (w1 = 1 - beta1, w2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): formed in double by the caller)
 int sahs_adam_step_launch(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float w1, float beta2, float w2,
                           float step_size, float bc2_sqrt, float eps, float grad_scale, hipStream_t stream);

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
 #include "sahs_launchers.hpp"
+#include "bf16_io.hpp"
 
 namespace sahs {
 
@@ -219,38 +220,7 @@ __global__ void __launch_bounds__(256) spade_backward_apply_kernel(long hw, cons
 // above, and each result is rounded to bf16 ONCE, on store (round to nearest even).  Traffic halves: 2 B read for the statistics + 6 B
 // read + 2 B written = 10 B per element forward, 8 B read per pass + 6 B written = 22 B backward.  W = 8: one 16-byte access (8 bf16)
 // per operand and thread, for hw % 8 == 0 and 16-byte aligned pointers; W = 1: element by element.  One loop body serves both.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bf16_widen(unsigned bits) { return __builtin_bit_cast(float, bits << 16); }
-__device__ __forceinline__ unsigned bf16_round(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }      // as pack.hip: f32_to_bf16_rne
-
-// group i (W elements) of a plane that starts at p
-template <int W>
-__device__ __forceinline__ void bf16_load(const unsigned short *p, long i, float (&v)[W])
-{
-    if constexpr (W == 8) {
-        const u32x4 q = reinterpret_cast<const u32x4 *>(p)[i];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[2 * k] = __builtin_bit_cast(float, q[k] << 16);
-            v[2 * k + 1] = __builtin_bit_cast(float, q[k] & 0xffff0000u);
-        }
-    } else {
-        v[0] = bf16_widen(p[i]);
-    }
-}
-template <int W>
-__device__ __forceinline__ void bf16_store(unsigned short *p, long i, const float (&v)[W])
-{
-    if constexpr (W == 8) {
-        u32x4 q;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) q[k] = bf16_round(v[2 * k]) | bf16_round(v[2 * k + 1]) << 16;
-        reinterpret_cast<u32x4 *>(p)[i] = q;
-    } else {
-        p[i] = (unsigned short)bf16_round(v[0]);
-    }
-}
+// (bf16_load / bf16_store of group i, W elements, of a plane: bf16_io.hpp)
 
 template <int W>
 __global__ void __launch_bounds__(256) instance_stats_bf16_kernel(long hw, const unsigned short *__restrict__ x, float *__restrict__ part, int pass)

@@ -8,7 +8,8 @@ BY NAME (_save_named / _load_named; None = absent).  Its backward (_RenderBackwa
 issues the same steps on one stream or, for the per-layer walks of "shared", pairwise on two, and returns gradients for the flat parameter
 buffer and the driving input.  Importance resampling is not differentiated (the reference detaches it, train_utils.py:164).  The stand-alone
 seams are differentiable too: ``FieldFn`` behind model(level, x, driving, pose), ``CompositeFn`` behind volume_render_radiance_field.
-Stage II: ``SpadeModulateFn`` behind spade_modulate, taken only when one of its tensors needs a gradient.
+Stage II: ``SpadeModulateFn`` behind spade_modulate, taken only when one of its tensors needs a gradient; ``SpectralNormalizeFn`` behind
+spectral_normalize (a list of weights in, their spectral-normalised forms out, one node), under the same rule.
 """
 import ctypes
 import os
@@ -394,6 +395,78 @@ def spade_modulate(x, gamma, beta, eps=1e-5, slope=1.0):
     return _spade_modulate_forward(x, gamma, beta, eps, slope)[2]
 
 
+SPECTRAL_NORM_MAX_JOBS = 32      # include/sahs_nerf.h: SAHS_SPECTRAL_NORM_MAX_JOBS
+
+
+def _flat_views(shapes, dtype, device):
+    """One allocation cut into contiguous tensors of ``shapes``, each starting on a 32-byte boundary -> the list of views."""
+    sizes = [torch.Size(s).numel() for s in shapes]
+    starts, total = [], 0
+    for n in sizes:
+        starts.append(total)
+        total += (n + 7) // 8 * 8
+    flat = torch.empty(total, dtype=dtype, device=device)
+    return [flat[a:a + n].view(s) for a, n, s in zip(starts, sizes, shapes)]
+
+
+def _pointer_table(tensors):
+    return (ctypes.c_void_p * len(tensors))(*(t.data_ptr() for t in tensors))
+
+
+def _spectral_norm_dims(weights):
+    return [(int(W.shape[0]), W.numel() // int(W.shape[0])) for W in weights]
+
+
+def _spectral_normalize_forward(weights, us, vs, training, eps, out_dtype):
+    """-> (the weights as the kernels read them, the outputs, each job's saved area: h + w + 1 floats u, v, sigma)."""
+    Ws = []
+    for k, (W, u, v) in enumerate(zip(weights, us, vs)):
+        W = _req(W, "spectral_normalize: weights[%d]" % k)
+        if W.dim() < 1 or W.numel() == 0:
+            raise _lib.SahsError("spectral_normalize: weights[%d] of shape %s has no rows or no columns" % (k, tuple(W.shape)))
+        h, w = _spectral_norm_dims([W])[0]
+        for name, t, n in (("us", u, h), ("vs", v, w)):
+            _req(t, "spectral_normalize: %s[%d]" % (name, k))
+            if tuple(t.shape) != (n,) or not t.is_contiguous():
+                raise _lib.SahsError("spectral_normalize: %s[%d] must be a contiguous vector of %d floats (it is updated in place), got shape %s"
+                                     % (name, k, n, tuple(t.shape)))
+        Ws.append(W)
+    dims = _spectral_norm_dims(Ws)
+    outs = _flat_views([W.shape for W in Ws], out_dtype, Ws[0].device)
+    saved = _flat_views([(h + w + 1,) for h, w in dims], torch.float32, Ws[0].device)
+    f = _lib.lib().sahs_spectral_norm_forward
+    for a in range(0, len(Ws), SPECTRAL_NORM_MAX_JOBS):
+        cut = slice(a, a + SPECTRAL_NORM_MAX_JOBS)
+        hs, ws = zip(*dims[cut])
+        n = len(hs)
+        check(f(n, _pointer_table(Ws[cut]), _pointer_table(us[cut]), _pointer_table(vs[cut]), _pointer_table(outs[cut]),
+                _pointer_table(saved[cut]), (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), int(out_dtype == torch.bfloat16),
+                int(bool(training)), float(eps), _stream()), "sahs_spectral_norm_forward")
+    return Ws, outs, saved
+
+
+def spectral_normalize(weights, us, vs, training, eps=1e-12):
+    """torch.nn.utils.spectral_norm's weight computation (dim 0, one power iteration) for a LIST of weights in two launches per 32 of them
+    (include/sahs_nerf.h: sahs_spectral_norm_forward): -> the list of W / sigma, each in its weight's shape.  ``us`` / ``vs``: each
+    weight's u (out channels) and v (the rest) vectors; training: they take one power iteration IN PLACE, as the module's buffers do;
+    otherwise they are only read.  Differentiable (SpectralNormalizeFn: one node, one backward launch per 32 weights) when grad mode
+    is on and a weight requires a gradient; otherwise the forward launches alone.
+    dtype: weights, us, vs float32, anything else is refused; sigma is formed in fp32 whatever autocast says, and the outputs are
+    bfloat16 -- the fp32 quotient rounded once, what autocast's cast of torch's result gives -- exactly when CUDA autocast is on with
+    dtype bfloat16, float32 otherwise.  The op itself runs outside autocast."""
+    weights, us, vs = list(weights), list(us), list(vs)
+    if not len(weights) == len(us) == len(vs):
+        raise _lib.SahsError("spectral_normalize: %d weights, %d us, %d vs: the lists must be of one length" % (len(weights), len(us), len(vs)))
+    if not weights:
+        return []
+    bf16 = torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+    out_dtype = torch.bfloat16 if bf16 else torch.float32
+    with torch.autocast("cuda", enabled=False):
+        if torch.is_grad_enabled() and any(isinstance(W, torch.Tensor) and W.requires_grad for W in weights):
+            return list(SpectralNormalizeFn.apply(us, vs, bool(training), float(eps), out_dtype, *weights))
+        return _spectral_normalize_forward(weights, us, vs, training, eps, out_dtype)[1]
+
+
 def adam_step(params, grad, exp_avg, exp_avg_sq, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, grad_scale=1.0):
     """One torch.optim.Adam update (weight_decay 0, no amsgrad) of n contiguous fp32 values, in place on params / exp_avg / exp_avg_sq, as one
     HIP launch (include/sahs_nerf.h: sahs_adam_step).  step: the 1-based count of this update; grad is read as grad * grad_scale."""
@@ -756,6 +829,52 @@ class SpadeModulateFn(torch.autograd.Function):
         check(f(planes, hw, _p(s.x), _p(s.gamma), _p(s.out), _p(s.stats), _p(grad_out), float(ctx.eps), float(ctx.slope), _p(dx), _p(dgamma),
                 _p(dbeta), _p(work), _stream()), name)
         return dx, dgamma, dbeta, None, None
+
+
+class SpectralNormalizeFn(torch.autograd.Function):
+    """spectral_normalize as ONE differentiable node with N weights in and N normalised weights out (Stage-II refiner training), in place
+    of six autograd nodes per weight: dW = G / sigma - (sum(G o W) / sigma^2) u v^T (include/sahs_nerf.h: sahs_spectral_norm_backward),
+    one launch per 32 weights.  Saved: the weights as read and each job's saved area -- the u, v, sigma that formed ITS output, so the
+    module's buffers may move on before the backward runs.  Gradients are formed only for the weights that ask for one and whose output
+    got one; each grad_out must come in the output's dtype.  Not twice differentiable."""
+    LEADING = 5      # us, vs, training, eps, out_dtype come before the weights
+
+    @staticmethod
+    def forward(ctx, us, vs, training, eps, out_dtype, *weights):
+        Ws, outs, saved = _spectral_normalize_forward(weights, us, vs, training, eps, out_dtype)
+        named = {"weight%d" % k: W.detach() for k, W in enumerate(Ws)}
+        named.update(("saved%d" % k, s) for k, s in enumerate(saved))
+        _save_named(ctx, **named)
+        ctx.out_dtype = out_dtype
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        s = _load_named(ctx)
+        lead = SpectralNormalizeFn.LEADING
+        jobs = [k for k, g in enumerate(grads) if g is not None and ctx.needs_input_grad[lead + k]]
+        Ws = [getattr(s, "weight%d" % k) for k in jobs]
+        Gs = [_req(grads[k], "SpectralNormalizeFn.backward: grad_out[%d]" % k, ctx.out_dtype) for k in jobs]
+        for k, W, G in zip(jobs, Ws, Gs):
+            if G.shape != W.shape:
+                raise _lib.SahsError("SpectralNormalizeFn.backward: gradient %d of shape %s for an output of shape %s" % (k, tuple(G.shape), tuple(W.shape)))
+        out = [None] * len(grads)
+        if jobs:
+            saved, dims = [getattr(s, "saved%d" % k) for k in jobs], _spectral_norm_dims(Ws)
+            dWs = _flat_views([W.shape for W in Ws], torch.float32, Ws[0].device)
+            f = _lib.lib().sahs_spectral_norm_backward
+            for a in range(0, len(jobs), SPECTRAL_NORM_MAX_JOBS):
+                cut = slice(a, a + SPECTRAL_NORM_MAX_JOBS)
+                hs, ws = zip(*dims[cut])
+                n = len(hs)
+                check(f(n, _pointer_table(Ws[cut]), _pointer_table(saved[cut]), _pointer_table(Gs[cut]), _pointer_table(dWs[cut]),
+                        (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), int(ctx.out_dtype == torch.bfloat16), _stream()),
+                      "sahs_spectral_norm_backward")
+            for k, dW in zip(jobs, dWs):
+                out[k] = dW
+        return (None,) * lead + tuple(out)
 
 
 class FieldFn(torch.autograd.Function):

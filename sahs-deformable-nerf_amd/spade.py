@@ -6,7 +6,8 @@ What runs where (DESIGN.md sections 8, 9): the 3x3 convolutions are library work
 forward and backward, in fp32 and under bf16 autocast.  That was judged for the fp32 forward and has since been measured for the bf16
 backward: of the 231 ms autocast training step the GPU works 29 ms, the library's bf16 convolution backward is faster than its fp32
 one, and MFMA kernels written for it were 2 ms per step slower than the library's (the step's 200 ms are host time of spectral norm's
-bf16 matrix-vector products: section 9).  The normalise / modulate / activate chain between them, which the reference runs as
+bf16 matrix-vector products: section 9; ``fuse_spectral_norm_`` is the opt-in that takes them, and torch's ~350 small launches per step,
+onto one fused op with sigma in fp32).  The normalise / modulate / activate chain between them, which the reference runs as
 six elementwise passes, is ONE fused HIP kernel behind a statistics pass (``ops.spade_modulate``).  It is differentiable -- a fused
 two-launch backward in place of six autograd nodes per SPADE layer -- so the generators train: ``refine_step`` is the step of the
 reference's train_get_texture_photo.py / train_get_texture_photo_audio.py (clamp, MSE, Adam; the discriminator and the VGG loss that
@@ -18,6 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.utils import spectral_norm
+from torch.nn.utils.spectral_norm import SpectralNorm
 
 from . import ops
 
@@ -221,6 +223,60 @@ class Generator_audio(nn.Module):
         fid1, fid2, _ = self.idencoder(I_src)
         code = self.AudioNet(driving_data.unsqueeze(0))                       # (1, 64)
         return self.refine_network(I_raw, fid1, fid2, TiledCodeMap(code, IdEncoder.WIDTHS[2], 64, 64))
+
+
+class _FusedSpectralNorm:
+    """The ONE forward pre-hook fuse_spectral_norm_ leaves on a module: every spectral-normalised submodule's weight from
+    ``ops.spectral_normalize`` -- two launches and one autograd node for all of them, sigma in fp32 whatever autocast says -- where
+    torch's per-module hooks run ~14 launches and 6 nodes each.  ``entries``: (submodule, its key in _forward_pre_hooks, torch's hook)
+    -- what unfuse_spectral_norm_ puts back.  It holds the submodules themselves, so a deepcopy of the hooked module (which copies this
+    object with the same memo) drives the copy's submodules."""
+
+    def __init__(self, entries):
+        self.entries = entries
+
+    def __call__(self, module, inputs):
+        groups = {}      # torch's hook iterates when ITS module trains, with its own eps: one call per (training, eps) met -- usually one
+        for m, _, hook in self.entries:
+            groups.setdefault((m.training, hook.eps), []).append((m, hook.name))
+        for (training, eps), group in groups.items():
+            get = lambda suffix: [getattr(m, name + suffix) for m, name in group]
+            for (m, name), weight in zip(group, ops.spectral_normalize(get("_orig"), get("_u"), get("_v"), training, eps=eps)):
+                setattr(m, name, weight)
+
+
+def _fused_hook_key(module):
+    return next((k for k, hook in module._forward_pre_hooks.items() if isinstance(hook, _FusedSpectralNorm)), None)
+
+
+def fuse_spectral_norm_(module):
+    """Opt-in, in place: take torch's SpectralNorm forward pre-hooks off every submodule of ``module`` (each found once, under
+    whatever names it is registered) and put one hook on ``module`` that normalises all their weights with the fused op before its
+    forward.  Parameters, buffers, state_dict and load_state_dict are untouched -- weight_orig, weight_u, weight_v stay where torch put
+    them, an optimiser built before stays valid -- and refine_step works as it is, with and without autocast_dtype.  Already fused, or
+    nothing to fuse: returns ``module`` as it is.  Hooks with n_power_iterations != 1 or dim != 0 are refused before anything changes."""
+    if _fused_hook_key(module) is not None:
+        return module
+    named = [(name, m, key, hook) for name, m in module.named_modules() for key, hook in m._forward_pre_hooks.items()
+             if isinstance(hook, SpectralNorm)]
+    for name, _, _, hook in named:
+        if hook.n_power_iterations != 1 or hook.dim != 0:
+            raise ValueError("fuse_spectral_norm_: %s has spectral norm with n_power_iterations=%d, dim=%d; the fused op is "
+                             "n_power_iterations=1, dim=0" % (name or "the module itself", hook.n_power_iterations, hook.dim))
+    if named:
+        for _, m, key, _ in named:
+            del m._forward_pre_hooks[key]
+        module.register_forward_pre_hook(_FusedSpectralNorm([(m, key, hook) for _, m, key, hook in named]))
+    return module
+
+
+def unfuse_spectral_norm_(module):
+    """Undo fuse_spectral_norm_: torch's hooks back on the submodules, the fused hook off ``module``.  Not fused: returns it as it is."""
+    key = _fused_hook_key(module)
+    if key is not None:
+        for m, k, hook in module._forward_pre_hooks.pop(key).entries:
+            m._forward_pre_hooks[k] = hook
+    return module
 
 
 def refine_learning_rate(cfg, epoch):

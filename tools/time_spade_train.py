@@ -20,6 +20,17 @@ autocast with the op swapped for the six torch ops.  For each: the training step
 bf16 through the C ABI (20 / 44 and 10 / 22 B per element), and the six ops on bf16 tensors for scale.  The file records whether autocast
 with the fused op is not slower than autocast with the swapped op, and the bf16 op not slower than the fp32 op, each beyond the run's
 own min-max spread; nothing is tuned to make them hold.
+
+  python tools/time_spade_train.py --spectral-norm [--size 512] [...] [--out profiles/spade_sn_step.json]
+
+What the fused spectral norm buys (``spade.fuse_spectral_norm_``; profiles/spade_sn_step.json).  Four variants of the ``Generator`` step,
+alternated round by round in one process: (a) fp32 with torch's hooks, (b) fp32 fused, (c) autocast bf16 with torch's hooks and
+``SpectralNorm.compute_weight`` run outside autocast -- an experiment defined here, the baseline for what the KERNEL buys, since a
+one-line autocast guard gives that much -- and (d) autocast bf16 fused; one round of today's autocast step with plain hooks, for the
+record.  And the op alone: the 18 matrices of ``Generator`` in one forward and one backward call through the C ABI on preallocated
+buffers, by HIP events, against ``SpectralNorm.compute_weight`` in fp32 plus its autograd backward over the same 18 weights.  The file
+records whether (d) is faster than (a), (d) and (b) not slower than (c) and (a), and the op faster than torch's chain, each beyond the
+run's own min-max spread; nothing is tuned to make them hold.
 There is no CPU path: without a GPU this fails.
 """
 import argparse
@@ -173,6 +184,124 @@ def main_autocast(args):
     print(json.dumps(result))
 
 
+def faster(a, b):
+    """a is faster than b beyond the run's own min-max spread: even its slowest round beats b's fastest."""
+    return max(a) < min(b)
+
+
+class hooks_outside_autocast:
+    """Variant (c): while entered, torch's SpectralNorm.compute_weight runs with autocast switched off (its matrix-vector products in fp32)."""
+
+    def __enter__(self):
+        from torch.nn.utils.spectral_norm import SpectralNorm
+        self.cls, self.own = SpectralNorm, SpectralNorm.compute_weight
+        own = self.own
+
+        def guarded(hook, module, do_power_iteration):
+            with torch.autocast("cuda", enabled=False):
+                return own(hook, module, do_power_iteration)
+
+        SpectralNorm.compute_weight = guarded
+
+    def __exit__(self, *exc):
+        self.cls.compute_weight = self.own
+
+
+def main_spectral_norm(args):
+    """--spectral-norm: variants (a) .. (d) of the step and the op alone (module docstring) -> profiles/spade_sn_step.json."""
+    import contextlib
+    from torch.nn.utils.spectral_norm import SpectralNorm
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(1)
+    torch.manual_seed(1)
+    #           (fused, refine_step's autocast_dtype, the context the steps run in)
+    variants = {"a_fp32_hooks": (False, None, contextlib.nullcontext), "b_fp32_fused": (True, None, contextlib.nullcontext),
+                "c_autocast_hooks_outside_autocast": (False, torch.bfloat16, hooks_outside_autocast),
+                "d_autocast_fused": (True, torch.bfloat16, contextlib.nullcontext)}
+    first = spade.Generator().to(dev).train()
+    nets = {k: copy.deepcopy(first) for k in variants}
+    nets["autocast_plain_hooks"] = first
+    for k, (fused, _, _) in variants.items():
+        if fused:
+            spade.fuse_spectral_norm_(nets[k])
+    opts = {k: torch.optim.Adam(G.parameters(), lr=2e-4, betas=(0.5, 0.999)) for k, G in nets.items()}
+    inputs = tuple(torch.rand(1, 3, args.size, args.size, device=dev, generator=gen) for _ in range(3))
+    res = {k: {"train_ms_per_step": []} for k in variants}
+    for k, (_, dt, ctx) in variants.items():      # warm-up: MIOpen picks its algorithms (per dtype), Adam allocates its state
+        with ctx():
+            res[k]["first_loss"] = steps_ms(nets[k], opts[k], inputs, args.warmup, autocast_dtype=dt)[1]
+    for _ in range(args.rounds):
+        for k, (_, dt, ctx) in variants.items():
+            with ctx():
+                res[k]["train_ms_per_step"].append(steps_ms(nets[k], opts[k], inputs, args.steps, autocast_dtype=dt)[0])
+    for k in variants:
+        res[k]["train_ms_per_step_best"] = min(res[k]["train_ms_per_step"])
+    k = "autocast_plain_hooks"      # today's autocast step (the power iteration in bf16): one round, for the record
+    steps_ms(nets[k], opts[k], inputs, args.warmup, autocast_dtype=torch.bfloat16)
+    res[k] = {"train_ms_per_step": [steps_ms(nets[k], opts[k], inputs, args.steps, autocast_dtype=torch.bfloat16)[0]]}
+    # the op alone: Generator's 18 normalised weights, one forward and one backward call through the C ABI on preallocated buffers
+    import ctypes
+    convs = [m for m in first.modules() if any(isinstance(h, SpectralNorm) for h in m._forward_pre_hooks.values())]
+    Ws = [m.weight_orig.detach().clone() for m in convs]
+    dims = [(W.shape[0], W.numel() // W.shape[0]) for W in Ws]
+    us, vs = [m.weight_u.clone() for m in convs], [m.weight_v.clone() for m in convs]
+    Gs = [torch.randn(W.shape, device=dev, generator=gen) for W in Ws]
+    saved, dWs = [torch.empty(h + w + 1, device=dev) for h, w in dims], [torch.empty_like(W) for W in Ws]
+    table = lambda ts: (ctypes.c_void_p * len(ts))(*(t.data_ptr() for t in ts))
+    hs, ws = (ctypes.c_int * len(dims))(*(h for h, _ in dims)), (ctypes.c_int * len(dims))(*(w for _, w in dims))
+    L, st, n = _lib.lib(), ops._stream(), len(Ws)
+    op, calls = {}, {}
+    for tag, dtype in (("fused_fp32", torch.float32), ("fused_bf16", torch.bfloat16)):
+        outs, grads = [torch.empty(W.shape, dtype=dtype, device=dev) for W in Ws], [g.to(dtype) for g in Gs]
+        t = (table(Ws), table(us), table(vs), table(outs), table(saved), table(grads), table(dWs), outs, grads)
+        fwd = lambda t=t, b=int(dtype == torch.bfloat16): _lib.check(L.sahs_spectral_norm_forward(n, t[0], t[1], t[2], t[3], t[4], hs, ws, b, 1, 1e-12, st), "forward")
+        bwd = lambda t=t, b=int(dtype == torch.bfloat16): _lib.check(L.sahs_spectral_norm_backward(n, t[0], t[4], t[5], t[6], hs, ws, b, st), "backward")
+        fwd()
+        calls[tag] = (fwd, bwd)
+    holders = []
+    for W, u, v in zip(Ws, us, vs):
+        holder = torch.nn.Module()
+        holder.weight_orig = torch.nn.Parameter(W.clone())
+        holder.register_buffer("weight_u", u.clone())
+        holder.register_buffer("weight_v", v.clone())
+        holders.append(holder)
+    sn = SpectralNorm("weight", 1, 0, 1e-12)
+    torch_fwd = lambda: [sn.compute_weight(m, True) for m in holders]
+    graph = torch_fwd()
+    calls["torch_fp32"] = (torch_fwd, lambda: torch.autograd.grad(graph, [m.weight_orig for m in holders], Gs, retain_graph=True))
+    for tag in calls:
+        op[tag] = {"forward_ms": [], "backward_ms": []}
+    for _ in range(args.rounds):
+        for tag, (fwd, bwd) in calls.items():
+            reps = 50 if tag == "torch_fp32" else 200
+            op[tag]["forward_ms"].append(events_ms(fwd, reps))
+            op[tag]["backward_ms"].append(events_ms(bwd, reps))
+    op.update(shapes=[list(d) for d in dims], weights=sum(h * w for h, w in dims),
+              timing="HIP events on the launch stream: 200 C-ABI calls per round (forward: two launches; backward: one) over the 18 weights on "
+                     "preallocated buffers, power_iteration = 1; torch_fp32 = 50 calls of SpectralNorm.compute_weight over 18 holder modules "
+                     "(forward, building the graph as a training step does) and of torch.autograd.grad through it (backward), allocations "
+                     "and launch pacing included")
+    a, b, c, d = (res[k]["train_ms_per_step"] for k in variants)
+    checks = {"d_faster_than_a": faster(d, a), "d_not_slower_than_c": not_slower(d, c), "b_not_slower_than_a": not_slower(b, a),
+              "op_forward_faster_than_torch": faster(op["fused_fp32"]["forward_ms"], op["torch_fp32"]["forward_ms"]),
+              "op_backward_faster_than_torch": faster(op["fused_fp32"]["backward_ms"], op["torch_fp32"]["backward_ms"]),
+              "rule": "a is slower than b only if min(a's rounds) > max(b's rounds), faster only if max(a's rounds) < min(b's rounds): "
+                      "beyond the run's own min-max spread"}
+    reported = {"d_vs_autocast_plain_hooks_speedup": res["autocast_plain_hooks"]["train_ms_per_step"][0] / min(d),
+                "c_minus_d_ms_best": min(c) - min(d), "c_minus_d_ms_range": [min(c) - max(d), max(c) - min(d)],
+                "a_minus_b_ms_best": min(a) - min(b)}
+    result = {"command": "python tools/time_spade_train.py --spectral-norm --size %d --steps %d --warmup %d --rounds %d" % (args.size, args.steps, args.warmup, args.rounds),
+              "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
+              "workload": "Generator: refine_step in train() mode (forward, clamp, MSE, backward, Adam) on a %dx%d frame; convolutions on MIOpen and "
+                          "the fused SPADE modulation in every variant; parameters and Adam state fp32 in every variant" % (args.size, args.size),
+              "steps_per_window": args.steps, "rounds": args.rounds, "variants": res, "op": op, "checks": checks, "reported": reported}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+
+
 def events_ms(fn, reps):
     for _ in range(5):
         fn()
@@ -192,12 +321,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--autocast", choices=("bf16",), default=None)
+    ap.add_argument("--spectral-norm", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "spade_bf16_step.json" if args.autocast else "spade_train_step.json")
+        name = "spade_sn_step.json" if args.spectral_norm else "spade_bf16_step.json" if args.autocast else "spade_train_step.json"
+        args.out = os.path.join(REPO, "profiles", name)
     if not torch.cuda.is_available():
         raise SystemExit("time_spade_train.py needs a GPU: nothing here can be measured on a CPU")
+    if args.spectral_norm:
+        return main_spectral_norm(args)
     if args.autocast:
         return main_autocast(args)
     dev = torch.device("cuda:0")
