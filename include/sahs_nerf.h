@@ -426,6 +426,31 @@ int sahs_spectral_norm_forward(int jobs, const float *const *W, float *const *u,
 int sahs_spectral_norm_backward(int jobs, const float *const *W, const float *const *saved, const void *const *grad_out, float *const *dW,
                                 const int *h, const int *w, int grad_bf16, void *stream);
 
+/* ---- image metrics: L1, MSE and windowed SSIM of two image batches, fused (the reference scores frames with scikit-image: nerf/metrics.py) ----
+ * a, b: B images of H x W pixels and C channels (1 .. 4), both SAHS_IMAGE_U8 (unsigned bytes, scored as x / 255) or both SAHS_IMAGE_F32,
+ * each addressed by its own four ELEMENT strides stride[0..3] = (batch, row, column, channel), host arrays read before the call
+ * returns: (H, W, C) arrays, (B, C, H, W) network outputs and cropped views are read in place.  Strides are >= 0.
+ * SSIM is skimage.metrics.structural_similarity with its defaults and multichannel=True: a 7 x 7 uniform window, sample covariance
+ * (the 49/48 normalisation), C1 = (0.01 R)^2, C2 = (0.03 R)^2 with R = ssim_data_range in the units of x / 255 resp. the floats, and
+ * the mean over the (H - 6)(W - 6) windows that lie inside the image (its crop(S, 3).mean(), so no border mode enters), per channel,
+ * then over the channels.  Values outside [0, R] are not an error.
+ * out: B rows of 3 + C doubles, [mean SSIM, MSE, L1, SSIM of channel 0 .. C - 1]; MSE and L1 are means over H * W * C elements.
+ * workspace: sahs_image_metrics_workspace_bytes(B, H, W, C) bytes, 8-byte aligned (one record of C + 2 doubles per image and tile of
+ * SAHS_IMAGE_METRICS_TILE^2 window origins); 0 from the query means the shape is invalid.
+ * Two launches whatever B is, no atomics, every sum in a fixed order: results are bit-reproducible and a batch gives the bits of its
+ * single calls.  uint8: the window moments, sum |d| and sum d^2 are exact integers; fp32: the moments are centred (a shift per tile
+ * and channel) and summed in float64.
+ * Invalid, refused before any HIP call: a null a, b, stride array, out or workspace; B < 0 (B == 0 succeeds without a launch) or
+ * B * tiles >= 2^31; H < 7 or W < 7 (skimage raises there as well) or > 32768; C outside 1 .. 4; a dtype other than the two; a
+ * negative stride; ssim_data_range not finite or <= 0; a or b not aligned to its element, out or workspace not to 8 bytes;
+ * workspace_bytes below the query's value. */
+#define SAHS_IMAGE_U8 0
+#define SAHS_IMAGE_F32 1
+#define SAHS_IMAGE_METRICS_TILE 32
+size_t sahs_image_metrics_workspace_bytes(long B, int H, int W, int C);
+int sahs_image_metrics(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
+                       double ssim_data_range, double *out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- launch probe (opt-in measurement aid; the one exception to "never synchronises") ----
  * While armed on the calling thread, every FIELD-kernel launch the library makes (from any entry point above) is bracketed by two HIP
  * events recorded on the launch stream, up to `capacity` launches (further ones are counted as dropped and run unprobed).

@@ -83,6 +83,8 @@ SIGNATURES = {
     "sahs_spade_modulate_backward_bf16": (_I, [_L, _L, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "sahs_spectral_norm_forward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "sahs_spectral_norm_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "sahs_image_metrics_workspace_bytes": (ctypes.c_size_t, [_L, _I, _I, _I]),
+    "sahs_image_metrics": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
     "sahs_probe_arm": (_I, [_I]),
     "sahs_probe_disarm": (_I, []),
     "sahs_probe_count": (_I, []),

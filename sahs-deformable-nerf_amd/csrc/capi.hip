@@ -366,6 +366,50 @@ int sahs_spectral_norm_backward(int jobs, const float *const *W, const float *co
     return e ? hip_fail(who, e) : 0;
 }
 
+// image metrics: every refusal names what it refuses, before any HIP call
+static bool image_metrics_shape(long B, int H, int W, int C)
+{
+    return B >= 0 && H >= 7 && W >= 7 && H <= 32768 && W <= 32768 && C >= 1 && C <= 4 && B * sahs_image_metrics_tiles(H, W) < 2147483648L;
+}
+
+size_t sahs_image_metrics_workspace_bytes(long B, int H, int W, int C)
+{
+    return image_metrics_shape(B, H, W, C) ? (size_t)B * (size_t)sahs_image_metrics_tiles(H, W) * (size_t)(C + 2) * sizeof(double) : 0;
+}
+
+int sahs_image_metrics(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
+                       double ssim_data_range, double *out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "sahs_image_metrics";
+    if (dtype != SAHS_IMAGE_U8 && dtype != SAHS_IMAGE_F32)
+        return fail(1, "%s: dtype = %d, must be SAHS_IMAGE_U8 (0) or SAHS_IMAGE_F32 (1) (capi.hip:%d)", who, dtype, __LINE__);
+    if (H < 7 || W < 7 || H > 32768 || W > 32768)
+        return fail(1, "%s: images of %d x %d pixels, the 7 x 7 window needs 7 <= H, W (<= 32768) (capi.hip:%d)", who, H, W, __LINE__);
+    if (C < 1 || C > 4) return fail(1, "%s: C = %d channels, must be 1 .. 4 (capi.hip:%d)", who, C, __LINE__);
+    if (!image_metrics_shape(B, H, W, C))
+        return fail(1, "%s: B = %ld images, needs B >= 0 and B * tiles < 2^31 (capi.hip:%d)", who, B, __LINE__);
+    if (!(ssim_data_range > 0.0) || !std::isfinite(ssim_data_range))
+        return fail(1, "%s: ssim_data_range = %g, must be finite and > 0 (capi.hip:%d)", who, ssim_data_range, __LINE__);
+    if (B == 0) return 0;
+    if (!a || !b || !stride_a || !stride_b || !out || !workspace)
+        return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !a ? "a" : !b ? "b" : !stride_a ? "stride_a" : !stride_b ? "stride_b" :
+                    !out ? "out" : "workspace", __LINE__);
+    for (int k = 0; k < 4; ++k)
+        if (stride_a[k] < 0 || stride_b[k] < 0)
+            return fail(1, "%s: stride %d is negative (%ld, %ld) (capi.hip:%d)", who, k, stride_a[k], stride_b[k], __LINE__);
+    const uintptr_t elem = dtype == SAHS_IMAGE_F32 ? 3u : 0u;
+    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & elem) != 0)
+        return fail(1, "%s: a and b must be aligned to their 4-byte elements (capi.hip:%d)", who, __LINE__);
+    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7u) != 0)
+        return fail(1, "%s: out and workspace must be 8-byte aligned (capi.hip:%d)", who, __LINE__);
+    const size_t need = sahs_image_metrics_workspace_bytes(B, H, W, C);
+    if (workspace_bytes < need)
+        return fail(1, "%s: workspace of %zu bytes, needs %zu (sahs_image_metrics_workspace_bytes) (capi.hip:%d)", who, workspace_bytes, need, __LINE__);
+    int e = sahs_image_metrics_launch(a, b, dtype == SAHS_IMAGE_F32, B, H, W, C, stride_a, stride_b, ssim_data_range, out,
+                                      static_cast<double *>(workspace), (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
 int sahs_composite_forward_rows(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
                                 const float *bg, int white_background, float *weights, float *rows, int row_ld, int fine_pass, void *stream)
 {

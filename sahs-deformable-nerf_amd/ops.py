@@ -467,6 +467,48 @@ def spectral_normalize(weights, us, vs, training, eps=1e-12):
         return _spectral_normalize_forward(weights, us, vs, training, eps, out_dtype)[1]
 
 
+IMAGE_METRICS_TILE = 32      # include/sahs_nerf.h: SAHS_IMAGE_METRICS_TILE
+_IMAGE_DTYPES = {torch.uint8: 0, torch.float32: 1}      # SAHS_IMAGE_U8, SAHS_IMAGE_F32
+
+
+def image_metrics(a, b, data_range=1.0, ssim_data_range=None, channels_last=True):
+    """L1, MSE and windowed SSIM of two images or image batches in two launches (include/sahs_nerf.h: sahs_image_metrics).
+    a, b: GPU tensors of ONE shape, (H, W, C) or (B, H, W, C) -- with channels_last=False (C, H, W) or (B, C, H, W) -- C = 1 .. 4,
+    H, W >= 7, both torch.uint8 (scored as x / 255) or both torch.float32; any other dtype and a mixed pair are refused.  They are read
+    in place through their strides: transposed or cropped views cost no copy.
+    -> a float64 tensor on the device, (3 + C,) or (B, 3 + C): [mean SSIM, MSE, L1, SSIM of each channel].  SSIM is
+    skimage.metrics.structural_similarity with its defaults and multichannel=True (7x7 uniform window, sample covariance, mean over the
+    windows inside the image) at the data range ``ssim_data_range``, which defaults to ``data_range`` (metrics.py on why the two
+    are separate arguments; PSNR, which is where ``data_range`` itself enters, is formed there).  Bit-reproducible; a batch gives the
+    bits of its single calls.  No gradient."""
+    for t, name in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.SahsError("image_metrics: %s must be a GPU tensor (the HIP path has no CPU fallback)" % name)
+        if t.device.index != torch.cuda.current_device():
+            raise _lib.SahsError("image_metrics: %s lives on %s but the current device is cuda:%d" % (name, t.device, torch.cuda.current_device()))
+    if a.dtype != b.dtype or a.dtype not in _IMAGE_DTYPES:
+        raise _lib.SahsError("image_metrics: a and b must both be torch.uint8 or both torch.float32, got %s and %s" % (a.dtype, b.dtype))
+    if a.shape != b.shape or a.dim() not in (3, 4):
+        raise _lib.SahsError("image_metrics: a and b must have one shape, (H, W, C) or (B, H, W, C) (channels_last=False: (C, H, W) or "
+                             "(B, C, H, W)), got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    ssim_data_range = data_range if ssim_data_range is None else ssim_data_range
+    if not (float(data_range) > 0.0 and float(ssim_data_range) > 0.0):
+        raise _lib.SahsError("image_metrics: data_range = %r and ssim_data_range = %r must be > 0" % (data_range, ssim_data_range))
+    batched = a.dim() == 4
+    a, b = (a.detach(), b.detach()) if batched else (a.detach()[None], b.detach()[None])
+    if not channels_last:
+        a, b = a.permute(0, 2, 3, 1), b.permute(0, 2, 3, 1)      # views: the kernel reads through the strides
+    B, H, W, C = a.shape
+    L = _lib.lib()
+    out = torch.empty(B, 3 + C, dtype=torch.float64, device=a.device)
+    need = int(L.sahs_image_metrics_workspace_bytes(B, H, W, C))
+    work = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=a.device)
+    strides = [(ctypes.c_long * 4)(*t.stride()) for t in (a, b)]
+    check(L.sahs_image_metrics(_p(a), _p(b), _IMAGE_DTYPES[a.dtype], B, H, W, C, strides[0], strides[1], float(ssim_data_range), _p(out),
+                               _p(work), need, _stream()), "sahs_image_metrics")
+    return out if batched else out[0]
+
+
 def adam_step(params, grad, exp_avg, exp_avg_sq, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, grad_scale=1.0):
     """One torch.optim.Adam update (weight_decay 0, no amsgrad) of n contiguous fp32 values, in place on params / exp_avg / exp_avg_sq, as one
     HIP launch (include/sahs_nerf.h: sahs_adam_step).  step: the 1-based count of this update; grad is read as grad * grad_scale."""
