@@ -58,6 +58,14 @@ class EagerField:
     def lin(self, name, x):
         return F.linear(x, self.sd[name + ".weight"], self.sd[name + ".bias"])
 
+    def dense(self, act_name, lin_name, x, slope):
+        """One hidden layer: the linear map, then its (leaky) ReLU.  With `lin`, `act` and `encode` the seam a subclass overrides to restate
+        another arithmetic (tests/bf16_reference.py: the bf16 kernels' rounding points) without copying `forward`."""
+        return self.act(act_name, self.lin(lin_name, x), slope)
+
+    def encode(self, x, L, include_input=True):
+        return positional_encoding(x, L, include_input)
+
     def audionet(self, audio):
         """modules.py:68-73."""
         x = audio.unsqueeze(0)[:, 0:16, :].permute(0, 2, 1)
@@ -79,7 +87,7 @@ class EagerField:
         x = initial
         tag = "warp" if prefix.startswith("warp") else "hyper"
         for i in range(n_layers):
-            x = self.act("%s.%d" % (tag, i), self.lin("%s.%s.%d" % (prefix, list_name, i), torch.cat((x, initial), -1) if i == skip else x), 0.0)
+            x = self.dense("%s.%d" % (tag, i), "%s.%s.%d" % (prefix, list_name, i), torch.cat((x, initial), -1) if i == skip else x, 0.0)
         return self.lin("%s.%s" % (prefix, final), x)
 
     def grid(self, level, xyz):
@@ -92,11 +100,12 @@ class EagerField:
         N, C, H, W, D = s.shape
         return s.permute(0, 4, 3, 2, 1).reshape(N * H * W * D, C)
 
-    def forward(self, level, x, audio, pose, driving=None, pose36=None, taps=None):
+    def forward(self, level, x, audio, pose, driving=None, pose36=None, taps=None, given=None):
         """Optional hooks for the gradient tests (the default call is the reference's): ``driving`` (the per-frame conditioning vector
         AudioNet makes of ``audio``, or the expression) and ``pose36`` (the pose encoding) given precomputed instead of computed from
         ``audio`` / ``pose``, so that they can be autograd leaves; ``taps`` (a dict) receives the deformation nets' outputs "warped" (x')
-        and "amb" (w), the seam of the split evaluation."""
+        and "amb" (w), the seam of the split evaluation; ``given`` = dict(warped=x', amb=w) supplies that seam instead: the deformation nets
+        are skipped and the radiance nets are evaluated at the given x', w (amb is ignored by an architecture without an ambient coordinate)."""
         a = self.a
         P = x.shape[0]
         xyz, dirs = x[..., :3], x[..., 3:6]
@@ -108,31 +117,34 @@ class EagerField:
         pose36 = pose36.repeat(P, 1)        # :519-521 / :369-370
         L = a["L"]
         if a["deform"]:
-            initial = torch.cat((positional_encoding(xyz, L), driving, pose36), dim=1)
-            warped = xyz + torch.tanh(self.deform("warp_field_mlp", "layers_xyz", "fc_final", 6, 4, initial))     # :304-305
-            initial = torch.cat((positional_encoding(xyz, L), driving, pose36), dim=1)                           # PE recomputed, :310
-            amb = self.deform("hyper_sheep_mlp", "layers_ambient", "fc_ambient", 6, 4, initial)
+            if given is None:
+                initial = torch.cat((self.encode(xyz, L), driving, pose36), dim=1)
+                warped = xyz + torch.tanh(self.deform("warp_field_mlp", "layers_xyz", "fc_final", 6, 4, initial))     # :304-305
+                initial = torch.cat((self.encode(xyz, L), driving, pose36), dim=1)                                       # PE recomputed, :310
+                amb = self.deform("hyper_sheep_mlp", "layers_ambient", "fc_ambient", 6, 4, initial)
+            else:
+                warped, amb = given["warped"], given["amb"]
             if taps is not None:
                 taps["warped"], taps["amb"] = warped, amb
-            enc = torch.cat((positional_encoding(warped, L), positional_encoding(amb, a["L_amb"], a["amb_inc"])), dim=1)
+            enc = torch.cat((self.encode(warped, L), self.encode(amb, a["L_amb"], a["amb_inc"])), dim=1)
         else:
-            warped = xyz                                                                                          # :316-327
-            enc = positional_encoding(warped, L)
+            warped = xyz if given is None else given["warped"]                                                   # :316-327
+            enc = self.encode(warped, L)
         feats = self.grid(level, warped)
         p = "nerf_mlps.%s." % level
         init = torch.cat((enc, pose36 if a["trunk_pose"] else driving), dim=1)                                    # modules.py:255-267
         h = init
         for i in range(a["layers"]):
-            h = self.act("trunk.%d" % i, self.lin(p + "layers_xyz.%d" % i, torch.cat((h, init), -1) if i == 3 else h), 0.01)
+            h = self.dense("trunk.%d" % i, p + "layers_xyz.%d" % i, torch.cat((h, init), -1) if i == 3 else h, 0.01)
         feat = self.lin(p + "fc_feat", h)
         alpha = self.lin(p + "fc_alpha", feat)
-        c = torch.cat((feat, positional_encoding(dirs, 4), feats), -1)
+        c = torch.cat((feat, self.encode(dirs, 4), feats), -1)
         for i in range(4):
-            c = self.act("dir.%d" % i, self.lin(p + "layers_dir.%d" % i, c), 0.01)
+            c = self.dense("dir.%d" % i, p + "layers_dir.%d" % i, c, 0.01)
         rgb = self.lin(p + "fc_rgb", c)
         s = feat
         for i in range(4):
-            s = self.act("seg.%d" % i, self.lin(p + "layers_seg.%d" % i, s), 0.01)
+            s = self.dense("seg.%d" % i, p + "layers_seg.%d" % i, s, 0.01)
         return torch.cat((rgb, self.lin(p + "fc_seg", s), alpha), dim=-1)
 
 
