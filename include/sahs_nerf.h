@@ -451,6 +451,41 @@ size_t sahs_image_metrics_workspace_bytes(long B, int H, int W, int C);
 int sahs_image_metrics(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
                        double ssim_data_range, double *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- LPIPS (net = alex, v0.1): the scaling layer and the distance head, fused (the reference scores frames with the lpips package:
+ * nerf/metrics.py).  The five AlexNet feature maps between the two calls are the caller's convolutions (metrics.py: LPIPS).
+ * sahs_lpips_prepare -- a, b: B images of H x W pixels and 3 channels, both SAHS_IMAGE_U8 (taken as x / 255) or both SAHS_IMAGE_F32,
+ * addressed by four ELEMENT strides (batch, row, column, channel) as sahs_image_metrics addresses them.  out: ONE contiguous
+ * (2B, 3, H, W) fp32 tensor, rows [0, B) from a and rows [B, 2B) from b, every element written once:
+ *   x' = ((normalize ? 2x - 1 : x) - shift_c) / scale_c,   shift = (-0.030, -0.088, -0.188),  scale = (0.458, 0.448, 0.450),
+ * each step one correctly rounded fp32 operation.  normalize = 0 is the reference's call (images in [0, 1] passed as they are), 1 the
+ * metric's authors' (images mapped to [-1, 1] first).  One launch.
+ * sahs_lpips_distance -- job l (1 .. SAHS_LPIPS_MAX_JOBS of them, one per layer) is a contiguous (2B, C[l], h, w) NCHW fp32 feature
+ * tensor features[l] whose rows [0, B) belong to a and [B, 2B) to b, its C[l] channel weights weights[l] (fp32), and hw[l] = h * w.
+ * features, weights, C, hw are HOST arrays read before the call returns; the table travels to the kernels as arguments.  Per pixel,
+ * with na = sqrt(sum_c a_c^2) + 1e-10 and nb likewise,
+ *   d = sum_c w_c (a_c / na - b_c / nb)^2 = sum w a^2 / na^2 + sum w b^2 / nb^2 - 2 sum w a b / (na nb),
+ * the five channel sums in float64 (each feature value is read once); d_l is the mean of d over the layer's hw[l] pixels.
+ * out: B rows of 1 + SAHS_LPIPS_MAX_JOBS doubles, [sum_l d_l, d_0, d_1, ...] (0 for layers beyond `jobs`).  Equal features give exactly
+ * 0; a pixel whose features are all zero gives 0, not NaN.
+ * workspace: sahs_lpips_distance_workspace_bytes(jobs, B, hw) bytes, 8-byte aligned (one double per image, layer and tile of
+ * SAHS_LPIPS_TILE pixels); 0 from the query means the shapes are invalid.
+ * Two launches whatever B and jobs are, no atomics, every sum in a fixed order: results are bit-reproducible and a batch gives the
+ * bits of its single calls.
+ * Invalid, refused with a message that names it before any HIP call: a null pointer (B == 0 succeeds without a launch); B < 0;
+ * prepare: C != 3, a dtype other than the two, H or W < SAHS_LPIPS_MIN_SIDE (a smaller image leaves AlexNet's second max-pool
+ * nothing) or > 32768, a negative stride, a misaligned pointer; distance: jobs outside 1 .. SAHS_LPIPS_MAX_JOBS, C[l] outside
+ * 1 .. SAHS_LPIPS_MAX_CHANNELS, hw[l] outside 1 .. 2^30, B * tiles >= 2^31, a null or misaligned features[l] or weights[l],
+ * workspace_bytes below the query's value. */
+#define SAHS_LPIPS_TILE 256
+#define SAHS_LPIPS_MAX_JOBS 5
+#define SAHS_LPIPS_MAX_CHANNELS 1024
+#define SAHS_LPIPS_MIN_SIDE 31
+int sahs_lpips_prepare(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
+                       int normalize, float *out, void *stream);
+size_t sahs_lpips_distance_workspace_bytes(int jobs, long B, const long *hw);
+int sahs_lpips_distance(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
+                        double *out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- launch probe (opt-in measurement aid; the one exception to "never synchronises") ----
  * While armed on the calling thread, every FIELD-kernel launch the library makes (from any entry point above) is bracketed by two HIP
  * events recorded on the launch stream, up to `capacity` launches (further ones are counted as dropped and run unprobed).

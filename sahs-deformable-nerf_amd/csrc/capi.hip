@@ -410,6 +410,81 @@ int sahs_image_metrics(const void *a, const void *b, int dtype, long B, int H, i
     return e ? hip_fail(who, e) : 0;
 }
 
+// LPIPS, the scaling layer and the distance head: every refusal names what it refuses, before any HIP call
+int sahs_lpips_prepare(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
+                       int normalize, float *out, void *stream)
+{
+    const char *who = "sahs_lpips_prepare";
+    if (dtype != SAHS_IMAGE_U8 && dtype != SAHS_IMAGE_F32)
+        return fail(1, "%s: dtype = %d, must be SAHS_IMAGE_U8 (0) or SAHS_IMAGE_F32 (1) (capi.hip:%d)", who, dtype, __LINE__);
+    if (C != 3) return fail(1, "%s: C = %d channels, LPIPS scores RGB images: C must be 3 (capi.hip:%d)", who, C, __LINE__);
+    if (H < SAHS_LPIPS_MIN_SIDE || W < SAHS_LPIPS_MIN_SIDE || H > 32768 || W > 32768)
+        return fail(1, "%s: images of %d x %d pixels, AlexNet's second max-pool needs %d <= H, W (<= 32768) (capi.hip:%d)", who, H, W,
+                    SAHS_LPIPS_MIN_SIDE, __LINE__);
+    if (B < 0 || 2 * B * (long)H * W >= 2147483648L * 256)
+        return fail(1, "%s: B = %ld images, needs B >= 0 and 2 B H W < 2^39 (capi.hip:%d)", who, B, __LINE__);
+    if (B == 0) return 0;
+    if (!a || !b || !stride_a || !stride_b || !out)
+        return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !a ? "a" : !b ? "b" : !stride_a ? "stride_a" : !stride_b ? "stride_b" : "out",
+                    __LINE__);
+    for (int k = 0; k < 4; ++k)
+        if (stride_a[k] < 0 || stride_b[k] < 0)
+            return fail(1, "%s: stride %d is negative (%ld, %ld) (capi.hip:%d)", who, k, stride_a[k], stride_b[k], __LINE__);
+    const uintptr_t elem = dtype == SAHS_IMAGE_F32 ? 3u : 0u;
+    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & elem) != 0 || (reinterpret_cast<uintptr_t>(out) & 3u) != 0)
+        return fail(1, "%s: a, b and out must be aligned to their 4-byte elements (capi.hip:%d)", who, __LINE__);
+    int e = sahs_lpips_prepare_launch(a, b, dtype == SAHS_IMAGE_F32, B, H, W, stride_a, stride_b, normalize != 0, out, (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
+static bool lpips_distance_shape(int jobs, long B, const long *hw)
+{
+    if (jobs < 1 || jobs > SAHS_LPIPS_MAX_JOBS || B < 0 || !hw) return false;
+    for (int k = 0; k < jobs; ++k)
+        if (hw[k] < 1 || hw[k] > (1L << 30)) return false;
+    return B * sahs_lpips_distance_tiles(jobs, hw) < 2147483648L;
+}
+
+size_t sahs_lpips_distance_workspace_bytes(int jobs, long B, const long *hw)
+{
+    return lpips_distance_shape(jobs, B, hw) ? (size_t)B * (size_t)sahs_lpips_distance_tiles(jobs, hw) * sizeof(double) : 0;
+}
+
+int sahs_lpips_distance(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
+                        double *out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "sahs_lpips_distance";
+    if (jobs < 1 || jobs > SAHS_LPIPS_MAX_JOBS)
+        return fail(1, "%s: jobs = %d, must be 1 .. %d (capi.hip:%d)", who, jobs, SAHS_LPIPS_MAX_JOBS, __LINE__);
+    if (!C || !hw) return fail(1, "%s: null pointer for the table %s (capi.hip:%d)", who, !C ? "C" : "hw", __LINE__);
+    for (int k = 0; k < jobs; ++k) {
+        if (C[k] < 1 || C[k] > SAHS_LPIPS_MAX_CHANNELS)
+            return fail(1, "%s: job %d has C = %d channels, must be 1 .. %d (capi.hip:%d)", who, k, C[k], SAHS_LPIPS_MAX_CHANNELS, __LINE__);
+        if (hw[k] < 1 || hw[k] > (1L << 30))
+            return fail(1, "%s: job %d has hw = %ld pixels, must be 1 .. 2^30 (capi.hip:%d)", who, k, hw[k], __LINE__);
+    }
+    if (!lpips_distance_shape(jobs, B, hw))
+        return fail(1, "%s: B = %ld images, needs B >= 0 and B * tiles < 2^31 (capi.hip:%d)", who, B, __LINE__);
+    if (B == 0) return 0;
+    if (!features || !weights || !out || !workspace)
+        return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !features ? "features" : !weights ? "weights" : !out ? "out" : "workspace",
+                    __LINE__);
+    for (int k = 0; k < jobs; ++k) {
+        if (!features[k] || !weights[k])
+            return fail(1, "%s: null pointer %s[%d] (capi.hip:%d)", who, !features[k] ? "features" : "weights", k, __LINE__);
+        if (((reinterpret_cast<uintptr_t>(features[k]) | reinterpret_cast<uintptr_t>(weights[k])) & 3u) != 0)
+            return fail(1, "%s: features[%d] and weights[%d] must be aligned to their 4-byte elements (capi.hip:%d)", who, k, k, __LINE__);
+    }
+    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7u) != 0)
+        return fail(1, "%s: out and workspace must be 8-byte aligned (capi.hip:%d)", who, __LINE__);
+    const size_t need = sahs_lpips_distance_workspace_bytes(jobs, B, hw);
+    if (workspace_bytes < need)
+        return fail(1, "%s: workspace of %zu bytes, needs %zu (sahs_lpips_distance_workspace_bytes) (capi.hip:%d)", who, workspace_bytes, need,
+                    __LINE__);
+    int e = sahs_lpips_distance_launch(jobs, features, weights, C, hw, B, out, static_cast<double *>(workspace), (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
 int sahs_composite_forward_rows(long N, int S, const float *raw, const float *z, const float *rays, int ray_stride, const float *noise,
                                 const float *bg, int white_background, float *weights, float *rows, int row_ld, int fine_pass, void *stream)
 {

@@ -77,6 +77,12 @@ int sahs_spectral_norm_backward_launch(int jobs, const float *const *W, const fl
 long sahs_image_metrics_tiles(int H, int W);
 int sahs_image_metrics_launch(const void *a, const void *b, int is_float, long B, int H, int W, int C, const long *stride_a,
                               const long *stride_b, double ssim_data_range, double *out, double *records, hipStream_t stream);
+// lpips.hip (arguments already validated: capi.hip; records: B * sahs_lpips_distance_tiles(jobs, hw) doubles)
+int sahs_lpips_prepare_launch(const void *a, const void *b, int is_float, long B, int H, int W, const long *stride_a, const long *stride_b,
+                              int normalize, float *out, hipStream_t stream);
+long sahs_lpips_distance_tiles(int jobs, const long *hw);
+int sahs_lpips_distance_launch(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
+                               double *out, double *records, hipStream_t stream);
 // optim.hip (w1 =1 - beta1, w2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): formed in double by the caller)
 int sahs_adam_step_launch(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float w1, float beta2, float w2,
                           float step_size, float bc2_sqrt, float eps, float grad_scale, hipStream_t stream);

@@ -509,6 +509,69 @@ def image_metrics(a, b, data_range=1.0, ssim_data_range=None, channels_last=True
     return out if batched else out[0]
 
 
+LPIPS_TILE, LPIPS_MAX_JOBS, LPIPS_MAX_CHANNELS, LPIPS_MIN_SIDE = 256, 5, 1024, 31      # include/sahs_nerf.h: SAHS_LPIPS_*
+
+
+def lpips_prepare(a, b, normalize=False, channels_last=True):
+    """LPIPS's input stage in one launch (include/sahs_nerf.h: sahs_lpips_prepare).  a, b: GPU tensors of ONE shape, (H, W, 3) or
+    (B, H, W, 3) -- with channels_last=False (3, H, W) or (B, 3, H, W) -- H, W >= 31, both torch.uint8 (taken as x / 255) or both
+    torch.float32, read in place through their strides.  -> ONE contiguous (2B, 3, H, W) float32 tensor, rows [0, B) from a and
+    [B, 2B) from b, after the scaling layer (x - shift) / scale; normalize=True maps x -> 2x - 1 first (metrics.py: LPIPS on which
+    is whose convention).  No gradient."""
+    for t, name in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.SahsError("lpips_prepare: %s must be a GPU tensor (the HIP path has no CPU fallback)" % name)
+        if t.device.index != torch.cuda.current_device():
+            raise _lib.SahsError("lpips_prepare: %s lives on %s but the current device is cuda:%d" % (name, t.device, torch.cuda.current_device()))
+    if a.dtype != b.dtype or a.dtype not in _IMAGE_DTYPES:
+        raise _lib.SahsError("lpips_prepare: a and b must both be torch.uint8 or both torch.float32, got %s and %s" % (a.dtype, b.dtype))
+    if a.shape != b.shape or a.dim() not in (3, 4):
+        raise _lib.SahsError("lpips_prepare: a and b must have one shape, (H, W, 3) or (B, H, W, 3) (channels_last=False: (3, H, W) or "
+                             "(B, 3, H, W)), got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    a, b = (a.detach(), b.detach()) if a.dim() == 4 else (a.detach()[None], b.detach()[None])
+    if not channels_last:
+        a, b = a.permute(0, 2, 3, 1), b.permute(0, 2, 3, 1)      # views: the kernel reads through the strides
+    B, H, W, C = a.shape
+    out = torch.empty(2 * B, 3, H, W, dtype=torch.float32, device=a.device)
+    strides = [(ctypes.c_long * 4)(*t.stride()) for t in (a, b)]
+    check(_lib.lib().sahs_lpips_prepare(_p(a), _p(b), _IMAGE_DTYPES[a.dtype], B, H, W, C, strides[0], strides[1], int(bool(normalize)),
+                                        _p(out), _stream()), "sahs_lpips_prepare")
+    return out
+
+
+def lpips_distance(features, lin_weights):
+    """LPIPS's head over up to five layers in two launches (include/sahs_nerf.h: sahs_lpips_distance).  features: a list of
+    contiguous (2B, C_l, h_l, w_l) float32 GPU tensors whose rows [0, B) belong to one image batch and [B, 2B) to the other;
+    lin_weights: per layer its C_l channel weights (float32, any shape with C_l elements, e.g. (1, C_l, 1, 1)).
+    -> (B, 6) float64: [LPIPS, d_0 .. d_4] (d of layers not given: 0).  Bit-reproducible; a batch gives the bits of its single calls.
+    A tensor that is not contiguous float32 is refused, not copied.  No gradient."""
+    features, lin_weights = list(features), list(lin_weights)
+    if len(features) != len(lin_weights) or not 1 <= len(features) <= LPIPS_MAX_JOBS:
+        raise _lib.SahsError("lpips_distance: %d feature tensors and %d weight tensors: needs one weight tensor per layer and 1 .. %d layers"
+                             % (len(features), len(lin_weights), LPIPS_MAX_JOBS))
+    for l, (f, w) in enumerate(zip(features, lin_weights)):
+        for t, name in ((f, "features[%d]" % l), (w, "lin_weights[%d]" % l)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise _lib.SahsError("lpips_distance: %s must be a GPU tensor (the HIP path has no CPU fallback)" % name)
+            if t.device.index != torch.cuda.current_device():
+                raise _lib.SahsError("lpips_distance: %s lives on %s but the current device is cuda:%d" % (name, t.device, torch.cuda.current_device()))
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.SahsError("lpips_distance: %s must be contiguous float32 (features: NCHW), got %s with strides %s"
+                                     % (name, t.dtype, tuple(t.stride())))
+        if f.dim() != 4 or f.shape[0] != features[0].shape[0] or f.shape[0] % 2 or w.numel() != f.shape[1]:
+            raise _lib.SahsError("lpips_distance: features[%d] is %s with %d weights: needs (2B, C, h, w) with the 2B of features[0] and C weights"
+                                 % (l, tuple(f.shape), w.numel()))
+    n, B = len(features), features[0].shape[0] // 2
+    L = _lib.lib()
+    fp, wp = (ctypes.c_void_p * n)(*[f.data_ptr() for f in features]), (ctypes.c_void_p * n)(*[w.data_ptr() for w in lin_weights])
+    Cs, hw = (ctypes.c_int * n)(*[f.shape[1] for f in features]), (ctypes.c_long * n)(*[f.shape[2] * f.shape[3] for f in features])
+    out = torch.empty(B, 1 + LPIPS_MAX_JOBS, dtype=torch.float64, device=features[0].device)
+    need = int(L.sahs_lpips_distance_workspace_bytes(n, B, hw))
+    work = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=out.device)
+    check(L.sahs_lpips_distance(n, fp, wp, Cs, hw, B, _p(out), _p(work), need, _stream()), "sahs_lpips_distance")
+    return out
+
+
 def adam_step(params, grad, exp_avg, exp_avg_sq, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, grad_scale=1.0):
     """One torch.optim.Adam update (weight_decay 0, no amsgrad) of n contiguous fp32 values, in place on params / exp_avg / exp_avg_sq, as one
     HIP launch (include/sahs_nerf.h: sahs_adam_step).  step: the 1-based count of this update; grad is read as grad * grad_scale."""
