@@ -11,9 +11,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsahs_nerf.so")
-SOURCES = ["capi.hip", "pack.hip", "render_ops.hip", "spade_ops.hip", "spectral_norm.hip", "image_metrics.hip", "lpips.hip", "optim.hip", "field_f32.hip", "field_bf16w.hip", "field_bf16x3.hip", "field_bwd.hip", "field_bwd_gemm.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip", "train_bwd.hip"]
+SOURCES = ["capi.hip", "pack.hip", "render_ops.hip", "spade_ops.hip", "spectral_norm.hip", "image_metrics.hip", "lpips.hip", "optim.hip", "field_f32.hip", "field_bf16w.hip", "field_bf16x3.hip", "field_bwd.hip", "field_bwd_tn_jobs.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip", "train_bwd.hip"]
 # sources built again for the NeRFaceModel architectures (csrc/sahs_model.hpp: -DSAHS_MODEL=1 / 2, symbols suffixed _nf / _ns);
-# field_bwd_gemm.hip reads no layout constant and is built once (every model's field_bwd.hip calls its launchers)
+# field_bwd_tn_jobs.hip and field_bwd_gemm.hip, which it includes (ONE translation unit: apart, every kernel of both gets another prologue),
+# read no layout constant and are built once (every model's field_bwd.hip calls their launchers)
 MODEL_SOURCES = ["pack.hip", "field_f32.hip", "field_bwd.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip"]
 X3_SOURCES = ["field_bf16x3.hip"]      # NeRFaceModels: the split-operand kernels (SAHS_BF16X3; with deformation nets also the mixed precision's)
 MODEL1_SOURCES = ["field_bf16w.hip"]      # NeRFaceModel: the bf16 radiance nets (with deformation nets: those stay fp32; without: the whole net)
@@ -39,8 +40,8 @@ NO_SCRATCH = {"gemm_dma_kernel": 0, "_ZN4sahs24field_forward_f32_kernelILb0E": 0
               "field_backward_chain_rad_f32_kernel": 0, "field_backward_chain_def_f32_kernel": 0,
               "image_metrics_tile_kernel": 0,      # (its channel loop must stay a loop: unrolled, four channels' float64 accumulators spill)
               "lpips_prepare_kernel": 0, "lpips_distance_tile_kernel": 0, "lpips_distance_finalize_kernel": 0,      # (streaming; five float64 sums per thread)
-              # (the names above match by substring, whichever file or namespace a kernel lives in -- the gemm_* ones are in field_bwd_gemm.hip,
-              # built once -- and so every model's build; the NeRFaceModel instances of the fused walk's chains, spelled out)
+              # (the names above match by substring, whichever file or namespace a kernel lives in -- the gemm_* ones are in field_bwd_gemm.hip
+              # and field_bwd_tn_jobs.hip, built once -- and so every model's build; the NeRFaceModel instances of the fused walk's chains, spelled out)
               "_ZN7sahs_nf3bwc31field_backward_chain_rad_kernel": 0, "_ZN7sahs_nf3bwc31field_backward_chain_def_kernel": 0,
               "_ZN7sahs_ns3bwc31field_backward_chain_rad_kernel": 0, "_ZN7sahs_nf3bwf35field_backward_chain_rad_f32_kernel": 0,
               "_ZN7sahs_nf3bwf35field_backward_chain_def_f32_kernel": 0, "_ZN7sahs_ns3bwf35field_backward_chain_rad_f32_kernel": 0}
@@ -57,10 +58,11 @@ HAND_SCHEDULED = [("field_bf16w.hip", 0, "field_forward_bf16w_kernel"), ("field_
 # field_bf16w.hip (one wave per SIMD, 512 registers): MFMA accumulators must live in ARCH VGPRs.  Left to its heuristics the compiler
 # puts them in AGPRs, and every accumulator value the activation code touches then costs a v_accvgpr_read -- which, unlike plain VALU
 # work, does NOT hide under the wave's own MFMAs (tools/micro/mfma_valu_overlap.hip: 2 reads per MFMA = 55 cycles per MFMA instead of 36).
-# field_bwd_gemm.hip (and field_bwd.hip, whose kernels were built with it when the GEMMs lived there): no SLP vectorisation -- left on, the compiler packs the operand splits' subtractions into v_pk_add_f32, which is an
+# field_bwd_gemm.hip, field_bwd_tn_jobs.hip (its job-table kernels were part of field_bwd_gemm.hip) and field_bwd.hip (whose kernels were
+# built with them when the GEMMs lived there): no SLP vectorisation -- left on, the compiler packs the operand splits' subtractions into v_pk_add_f32, which is an
 # anti-lever beside MFMAs on this chip (MI355X_MICROARCH.md); without it the training step is 1.1 % faster (same-box A/B: 17.95 -> 17.75 ms).
 # The forward kernels measure neutral (+-0.5 %) and keep the default.
-PER_FILE_FLAGS = {"field_bwd_gemm.hip": ["-fno-slp-vectorize"], "field_bwd.hip": ["-fno-slp-vectorize"],
+PER_FILE_FLAGS = {"field_bwd_gemm.hip": ["-fno-slp-vectorize"], "field_bwd_tn_jobs.hip": ["-fno-slp-vectorize"], "field_bwd.hip": ["-fno-slp-vectorize"],
                   "field_bf16w.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "field_bf16x3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                   "field_bwd_chain.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-ffp-contract=off", "-fno-math-errno", "-Wall", "-Wno-unused-function"]

@@ -7,7 +7,8 @@
 //   over all samples of the call.  Not fused across layers: activations and per-layer gradients go through HBM;
 //   the fused walk (further down): the data-gradient chain in one kernel, every weight gradient of a part in one job table.
 // The GEMM kernels themselves, the job-table launches and the copy / axpy / constant-column helpers read no layout constant: they are
-// built once (field_bwd_gemm.hip) and called here through the launchers of field_bwd_gemm.hpp as sahs::...
+// built once -- the per-layer walk's GEMMs and the helpers in field_bwd_gemm.hip, the fused walk's job-table kernels in
+// field_bwd_tn_jobs.hip -- and called here through the launchers of field_bwd_gemm.hpp as sahs::...
 // Conventions follow autograd of the reference graph
 // (models.py:514-528, modules.py:371-390 / 444-462 / 254-295): the per-frame constant inputs (driving, pose
 // encoding) get their weight-column gradients from the bias gradient (their value is the same for every sample:
@@ -311,14 +312,8 @@ struct Bwd {
                 walo += words;
                 if (dry) {
                     if (ncopy < MAX_COPY_JOBS) copies.j[ncopy] = CopyJob{W, dst, ldw, 0, K, N, 1};
-                    ++ncopy;
+                    ++ncopy;       // (more than MAX_COPY_JOBS: flush_copies fails the walk before the real pass)
                     return;
-                }
-                if (ncopy > MAX_COPY_JOBS) {       // more jobs than a batch holds: pack one by one
-                    CopyBatch one;
-                    one.j[0] = CopyJob{W, dst, ldw, 0, K, N, 1};
-                    sahs::copy2d_batch(st, one, 1, 1);
-                    check();
                 }
                 W = dst; ldw = 0;
             } else if (!sahs::gemm_aligned(W, ldw)) {
@@ -328,13 +323,8 @@ struct Bwd {
                 walo += (long)K * ldb;
                 if (dry) {
                     if (ncopy < MAX_COPY_JOBS) copies.j[ncopy] = CopyJob{W, dst, ldw, ldb, K, N, 0};
-                    ++ncopy;       // (more than MAX_COPY_JOBS: the real pass copies one by one, as before)
+                    ++ncopy;
                     return;
-                }
-                if (ncopy > MAX_COPY_JOBS) {
-                    const long tot = (long)K * N;
-                    sahs::copy2d(st, (unsigned)((tot + 255) / 256), K, N, W, ldw, dst, ldb, 0);
-                    check();
                 }
                 W = dst; ldw = ldb;
             }
@@ -433,6 +423,7 @@ extern "C" int SAHS_SYM(sahs_field_backward_split_launch)(const float *flat, con
 #endif
     if (P > 4000000L) return -3;   // gridDim.y of the P x N GEMMs; callers chunk larger batches
     Bwd b{stream, P};
+    b.flat = flat; b.grad_flat = grad_flat;      // (what defer_consts addresses the weights and their gradient by)
     b.zero = ws + P * (256L * 3 + DIN_LD + 32 + 12) + DB_SCRATCH - 64;   // tail of the (zeroed) bias-gradient scratch, never written
     b.wal = ws + P * (256L * 3 + DIN_LD + 32 + 12) + DB_SCRATCH + 2 * GRID_FLOATS;
     b.wal_cap = WAL_FLOATS;
@@ -464,20 +455,14 @@ extern "C" int SAHS_SYM(sahs_field_backward_split_launch)(const float *flat, con
     // bias gradient of a layer: straight into the flat gradient (boff >= 0), or -- for the six layers whose folded per-frame
     // constants need this call's db on its own -- into a scratch slot that add_bias then adds
     auto newdb = [&](int n, long boff = -1) { if (boff >= 0) return G(boff); float *p = db + dbo; dbo += (n + 3) / 4 * 4; return p; };
+    // (the deferred tables are the fused walk's, Bwd::defer_add / defer_consts: a full table fails the walk)
     auto add_bias = [&](float *dbl, long boff, int n) {      // deferred to the end of the walk, batched (nothing in the walk reads G(boff))
         if (dbl == G(boff) || b.dry) return;
-        if (b.naxpy < MAX_AXPY_JOBS) { b.axpys.j[b.naxpy++] = AxpyJob{dbl, G(boff), n}; return; }
-        sahs::axpy(stream, 1, n, dbl, G(boff)); b.check();
+        b.defer_add(dbl, G(boff), n);
     };
     auto consts = [&](long woff, long ld, int rows, int col0, int cols, const float *dbl, const float *c, float *dc) {
         if (b.dry) return;
-        if (b.nconst < MAX_CONST_JOBS) {                     // deferred as well: dW's constant columns and dc are read by nothing in the walk
-            b.consts.j[b.nconst++] = ConstJob{W(woff), G(woff), dbl, c, dc, ld, rows, cols, col0};
-            b.const_maxcols = cols > b.const_maxcols ? cols : b.const_maxcols;
-            return;
-        }
-        sahs::const_cols(stream, rows, cols, W(woff), G(woff), ld, col0, dbl, c, dc);
-        b.check();
+        b.defer_consts(woff, ld, rows, col0, cols, dbl, c, dc);      // deferred as well: dW's constant columns and dc are read by nothing in the walk
     };
     // rows of a head's weights into its zero-padded 16-row copy (collected in the dry pass, one batched launch with the aligned weight
     // copies); rows of a head's gradient scratch added to the flat gradient (deferred to the end of the walk, batched)
@@ -489,8 +474,7 @@ extern "C" int SAHS_SYM(sahs_field_backward_split_launch)(const float *flat, con
     };
     auto head_add = [&](const float *src, float *dst, int n) {
         if (b.dry) return;
-        if (b.naxpy < MAX_AXPY_JOBS) { b.axpys.j[b.naxpy++] = AxpyJob{src, dst, n}; return; }
-        sahs::axpy(stream, (unsigned)((n + 255) / 256), n, src, dst); b.check();
+        b.defer_add(src, dst, n);
     };
     const float *A = actbuf;
     if (do_rad) {

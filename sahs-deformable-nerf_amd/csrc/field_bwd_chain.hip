@@ -9,7 +9,7 @@
 //   * the (leaky-)ReLU derivative taken from the sign bits the saving forward wrote (sahs_layout.hpp: sbits; 1 bit per value instead of the
 //     saved fp32 activation), applied as v_bfe_i32 + v_bfi_b32 on the value's way into the conversion,
 //   * every dZ tile stored once, fp32, into the plane of its layer (the act:: layout: dZ of a layer sits where its activation sits in
-//     the saved-activation buffer) -- the operands of the weight-gradient launch that follows (field_bwd_gemm.hip: gemm_tn_jobs_kernel).
+//     the saved-activation buffer) -- the operands of the weight-gradient launch that follows (field_bwd_tn_jobs.hip: gemm_tn_jobs_kernel).
 // Same arithmetic as the per-layer split-operand GEMMs it replaces (hi*hi + hi*lo + lo*hi, fp32 accumulation), a different summation
 // order.  Built once per model (sahs_model.hpp): the layer programs below follow each model's trunk (8 layers for the AudioFaceModel, 4 for
 // the NeRFaceModels, skip layer 3 in all) and the NeRFaceModel without deformation nets (SAHS_MODEL 2) has no deformation chain and no

@@ -7,7 +7,7 @@
 // tile of a layer (lane (q, j): gradients 4q..4q+3 of sample j) is the B operand of the next, the transposed weights stream L2 -> LDS by
 // LDS-DMA in <= 32 KB chunks.  The epilogue policy is the backward's: start from zero, multiply by the (leaky-)ReLU derivative read from
 // the sign bits the saving forward wrote (sahs_layout.hpp: sbits -- the forward's lane (q, j) wrote the very word this lane (q, j) reads),
-// store the dZ tile into the plane of its layer (the operand of the weight-gradient launch, field_bwd_gemm.hip: gemm_tn_jobs*_f32_kernel).
+// store the dZ tile into the plane of its layer (the operand of the weight-gradient launch, field_bwd_tn_jobs.hip: gemm_tn_jobs*_f32_kernel).
 // Same planes, seam buffers and launch order as the split-operand chain; sums in a different order than the per-layer GEMMs it replaces
 // (gemm_dma_kernel<false, false>), same exact products.  Built once per model, from the same layer table as field_bwd_chain.hip's programs (bwd_program.hpp).
 #include <hip/hip_runtime.h>

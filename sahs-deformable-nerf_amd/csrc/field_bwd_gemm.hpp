@@ -1,5 +1,6 @@
-// field_bwd_gemm.hpp -- host launchers of the backward's model-independent kernels (field_bwd_gemm.hip): the dense GEMMs of the
-// per-layer walk, the job-table weight-gradient launches of the fused walk, and the copy / axpy / constant-column helpers of both.
+// field_bwd_gemm.hpp -- host launchers of the backward's model-independent kernels: the dense GEMMs of the per-layer walk and the
+// copy / axpy / constant-column helpers of both walks (field_bwd_gemm.hip), the job-table weight-gradient launches of the fused walk
+// (field_bwd_tn_jobs.hip).
 //
 // None of them reads a layout constant, so they are built ONCE, in plain namespace sahs, and every model's field_bwd.hip calls them
 // as sahs::...  A kernel can only be launched from the translation unit that defines it: this header declares launchers and the job
@@ -56,6 +57,10 @@ struct CopyJob { const float *src; float *dst; long lds_, ldd; int K, N; int pac
 // fragment is one ds_read_b128, with no conversion work in the GEMM (columns past N are zero).  Pieces in (step, block) order.
 struct ConstJob { const float *W; float *dW; const float *db, *c; float *dc; long ld; int rows, cols, col0; };
 struct AxpyJob { const float *x; float *y; int n; };
+// A full table fails the walk (hipErrorOutOfMemory); no model comes near.  Jobs per flush, read off the walks in field_bwd.hip:
+//   per-layer walk, all parts   axpy 12 (6 head rows + the 6 layers with folded constants), const 10 (trunk 2, hyper 4, warp 4) for the
+//                               audio model and the NeRFaceModel; axpy 8, const 2 for the NeRFaceModel without deformation nets
+//   fused walk, radiance part   axpy 8, const 2 (every model);   deformation part   axpy 4, const 8
 constexpr int MAX_COPY_JOBS = 48, MAX_CONST_JOBS = 24, MAX_AXPY_JOBS = 24;
 struct CopyBatch { CopyJob j[MAX_COPY_JOBS]; };
 struct ConstBatch { ConstJob j[MAX_CONST_JOBS]; };
@@ -66,10 +71,8 @@ void copy2d(hipStream_t st, unsigned blocks, long M, int N, const float *src, lo
 // jobs 0 .. n-1 of the batch; phase 0: the plain copies, 1: the pack jobs (a pack job may read what a plain copy wrote)
 void copy2d_batch(hipStream_t st, const CopyBatch &b, int n, int phase);
 // per-frame constants: dW[r][col0 + k] += db[r] * c[k];  dc[k] += sum_r W[r][col0 + k] * db[r]
-void const_cols(hipStream_t st, int rows, int cols, const float *W, float *dW, long ld, int col0, const float *db, const float *c, float *dc);
 void const_cols_batch(hipStream_t st, const ConstBatch &b, int n);      // (cols <= 256 in every job)
-// y[i] += x[i] (atomic), on `blocks` workgroups / one workgroup per job
-void axpy(hipStream_t st, unsigned blocks, int n, const float *x, float *y);
+// y[i] += x[i] (atomic), one workgroup per job
 void axpy_batch(hipStream_t st, const AxpyBatch &b, int n);
 // y[i] += a[i] over n float4s
 void add_rows8(hipStream_t st, long n, const float *a, float *y);

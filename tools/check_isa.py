@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """ISA audit of one kernel: which memory instructions and waits the compiler put into it (runs here, no GPU).
 
-    python tools/check_isa.py field_bwd_gemm.hip gemm_dma_kernel
+    python tools/check_isa.py field_bwd_tn_jobs.hip gemm_dma_kernel      (the unit that is built: it includes field_bwd_gemm.hip)
+    python tools/check_isa.py field_bwd_tn_jobs.hip gemm_tn_jobs
     python tools/check_isa.py field_bf16w.hip field_forward_bf16w_kernel
 
 Compiles the source to gfx950 assembly with the product's flags (`build.py`), cuts out every function whose (mangled) name

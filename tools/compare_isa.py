@@ -3,7 +3,8 @@
     hipcc <the build's flags for that source> --cuda-device-only -S csrc/x.hip -o x.s      (tools/check_isa.py prints the command)
     python tools/compare_isa.py A.s B.s [kernel name pattern]
 
-Made for moving kernels between translation units (field_bwd.hip -> field_bwd_gemm.hip).  Byte equality is the wrong bar for that: a
+Made for moving kernels between translation units and files (field_bwd.hip -> field_bwd_gemm.hip -> field_bwd_tn_jobs.hip, which
+includes the former: one unit).  Byte equality is the wrong bar for that: a
 kernel that calls an out-of-line function (the job kernels' 64-bit division) gets the workgroup-id registers its ABI needs inferred from
 the whole translation unit, so scalar registers are renumbered and a prologue may gain or lose a v_mov_b32.  What is compared instead,
 per kernel present in both files (namespaces sahs / sahs_nf / sahs_ns / anonymous are folded into one):
