@@ -277,56 +277,55 @@ int sahs_adam_step(float *params, const float *grad, float *exp_avg, float *exp_
 }
 
 long sahs_spade_modulate_workspace_words(long planes) { return planes > 0 ? sahs_spade_stats_words(planes) : 0; }
+long sahs_spade_modulate_backward_workspace_words(long planes) { return planes > 0 ? sahs_spade_stats_words(planes) : 0; }
+
+// the fp32 and the bf16 entries (tensors as bf16 bit patterns; stats / work stay fp32) validate alike and refuse under their own names
+#define SPADE_REQUIRE(cond, what) do { if (!(cond)) return fail(1, "%s%s: invalid argument (capi.hip:%d)", who, what, __LINE__); } while (0)
+static int spade_forward(const char *who, int bf16, long planes, long hw, const void *x, const void *gamma, const void *beta, float eps,
+                         float slope, void *out, float *stats, void *stream)
+{
+    if (planes == 0 || hw == 0) return 0;
+    SPADE_REQUIRE(planes > 0 && hw > 0 && x && gamma && beta && out && stats && eps > 0.0f, "");
+    SPADE_REQUIRE(planes <= 65535, "(planes <= 65535: one plane per gridDim.y)");
+    int e = sahs_spade_modulate_launch(planes, hw, x, gamma, beta, eps, slope, out, stats, bf16, (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+static int spade_backward(const char *who, int bf16, long planes, long hw, const void *x, const void *gamma, const void *out, const float *stats,
+                          const void *grad_out, float eps, float slope, void *dx, void *dgamma, void *dbeta, float *work, void *stream)
+{
+    if (planes == 0 || hw == 0) return 0;
+    SPADE_REQUIRE(planes > 0 && hw > 0 && x && gamma && stats && grad_out && eps > 0.0f, "");
+    SPADE_REQUIRE(planes <= 65535, "(planes <= 65535: one plane per gridDim.y)");
+    SPADE_REQUIRE(slope >= 0.0f && (out || slope == 1.0f), "(slope >= 0; out may be null only for slope 1)");
+    SPADE_REQUIRE(dx || dgamma || dbeta, "(at least one of dx, dgamma, dbeta)");
+    SPADE_REQUIRE(work || !dx, "(dx needs the workspace)");
+    int e = sahs_spade_modulate_backward_launch(planes, hw, x, gamma, slope == 1.0f ? nullptr : out, stats, grad_out, eps, slope, dx, dgamma, dbeta,
+                                                work, bf16, (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+#undef SPADE_REQUIRE
 
 int sahs_spade_modulate(long planes, long hw, const float *x, const float *gamma, const float *beta, float eps, float slope, float *out,
                         float *stats, void *stream)
 {
-    if (planes == 0 || hw == 0) return 0;
-    REQUIRE(planes > 0 && planes <= 2147483647L && hw > 0 && x && gamma && beta && out && stats && eps > 0.0f, "sahs_spade_modulate");
-    int e = sahs_spade_modulate_launch(planes, hw, x, gamma, beta, eps, slope, out, stats, (hipStream_t)stream);
-    return e ? hip_fail("sahs_spade_modulate", e) : 0;
+    return spade_forward("sahs_spade_modulate", 0, planes, hw, x, gamma, beta, eps, slope, out, stats, stream);
 }
-
-long sahs_spade_modulate_backward_workspace_words(long planes) { return planes > 0 ? sahs_spade_stats_words(planes) : 0; }
-
 int sahs_spade_modulate_backward(long planes, long hw, const float *x, const float *gamma, const float *out, const float *stats,
                                  const float *grad_out, float eps, float slope, float *dx, float *dgamma, float *dbeta, float *work, void *stream)
 {
-    if (planes == 0 || hw == 0) return 0;
-    REQUIRE(planes > 0 && hw > 0 && x && gamma && stats && grad_out && eps > 0.0f, "sahs_spade_modulate_backward");
-    REQUIRE(planes <= 65535, "sahs_spade_modulate_backward(planes <= 65535: one plane per gridDim.y)");
-    REQUIRE(slope >= 0.0f && (out || slope == 1.0f), "sahs_spade_modulate_backward(slope >= 0; out may be null only for slope 1)");
-    REQUIRE(dx || dgamma || dbeta, "sahs_spade_modulate_backward(at least one of dx, dgamma, dbeta)");
-    REQUIRE(work || !dx, "sahs_spade_modulate_backward(dx needs the workspace)");
-    int e = sahs_spade_modulate_backward_launch(planes, hw, x, gamma, slope == 1.0f ? nullptr : out, stats, grad_out, eps, slope, dx, dgamma,
-                                                dbeta, work, (hipStream_t)stream);
-    return e ? hip_fail("sahs_spade_modulate_backward", e) : 0;
+    return spade_backward("sahs_spade_modulate_backward", 0, planes, hw, x, gamma, out, stats, grad_out, eps, slope, dx, dgamma, dbeta, work, stream);
 }
-
-// the bf16 forms (tensors as bf16 bit patterns; stats / work stay fp32): both refuse by name what the fp32 backward refuses
 int sahs_spade_modulate_bf16(long planes, long hw, const unsigned short *x, const unsigned short *gamma, const unsigned short *beta, float eps,
                              float slope, unsigned short *out, float *stats, void *stream)
 {
-    if (planes == 0 || hw == 0) return 0;
-    REQUIRE(planes > 0 && hw > 0 && x && gamma && beta && out && stats && eps > 0.0f, "sahs_spade_modulate_bf16");
-    REQUIRE(planes <= 65535, "sahs_spade_modulate_bf16(planes <= 65535: one plane per gridDim.y)");
-    int e = sahs_spade_modulate_bf16_launch(planes, hw, x, gamma, beta, eps, slope, out, stats, (hipStream_t)stream);
-    return e ? hip_fail("sahs_spade_modulate_bf16", e) : 0;
+    return spade_forward("sahs_spade_modulate_bf16", 1, planes, hw, x, gamma, beta, eps, slope, out, stats, stream);
 }
-
 int sahs_spade_modulate_backward_bf16(long planes, long hw, const unsigned short *x, const unsigned short *gamma, const unsigned short *out,
                                       const float *stats, const unsigned short *grad_out, float eps, float slope, unsigned short *dx,
                                       unsigned short *dgamma, unsigned short *dbeta, float *work, void *stream)
 {
-    if (planes == 0 || hw == 0) return 0;
-    REQUIRE(planes > 0 && hw > 0 && x && gamma && stats && grad_out && eps > 0.0f, "sahs_spade_modulate_backward_bf16");
-    REQUIRE(planes <= 65535, "sahs_spade_modulate_backward_bf16(planes <= 65535: one plane per gridDim.y)");
-    REQUIRE(slope >= 0.0f && (out || slope == 1.0f), "sahs_spade_modulate_backward_bf16(slope >= 0; out may be null only for slope 1)");
-    REQUIRE(dx || dgamma || dbeta, "sahs_spade_modulate_backward_bf16(at least one of dx, dgamma, dbeta)");
-    REQUIRE(work || !dx, "sahs_spade_modulate_backward_bf16(dx needs the workspace)");
-    int e = sahs_spade_modulate_backward_bf16_launch(planes, hw, x, gamma, slope == 1.0f ? nullptr : out, stats, grad_out, eps, slope, dx,
-                                                     dgamma, dbeta, work, (hipStream_t)stream);
-    return e ? hip_fail("sahs_spade_modulate_backward_bf16", e) : 0;
+    return spade_backward("sahs_spade_modulate_backward_bf16", 1, planes, hw, x, gamma, out, stats, grad_out, eps, slope, dx, dgamma, dbeta, work,
+                          stream);
 }
 
 // the fused, batched spectral norm: the tables are host arrays of device pointers; every refusal names what it refuses

@@ -54,19 +54,13 @@ int sahs_route_xw_grad_launch(long N, int Sc, int nf, const int *src, const floa
 int sahs_resample_launch(long N, int S, int nf, int from_z, const float *z, const float *weights, const float *u, float *z_samples,
                          float *z_out, long long *inds, int *src, hipStream_t stream);
 int sahs_ray_uniforms_launch(unsigned long long seed, int stream_id, long ray0, long N, int S, float *out, hipStream_t stream);
-// spade_ops.hip
+// spade_ops.hip (the tensors: float, or with bf16 set bf16 bit patterns; stats and work: float for both)
 long sahs_spade_stats_words(long planes);
-int sahs_spade_modulate_launch(long planes, long hw, const float *x, const float *gamma, const float *beta, float eps, float slope, float *out,
-                               float *stats, hipStream_t stream);
-int sahs_spade_modulate_backward_launch(long planes, long hw, const float *x, const float *gamma, const float *out, const float *stats,
-                                        const float *grad, float eps, float slope, float *dx, float *dgamma, float *dbeta, float *work,
+int sahs_spade_modulate_launch(long planes, long hw, const void *x, const void *gamma, const void *beta, float eps, float slope, void *out,
+                               float *stats, int bf16, hipStream_t stream);
+int sahs_spade_modulate_backward_launch(long planes, long hw, const void *x, const void *gamma, const void *out, const float *stats,
+                                        const void *grad, float eps, float slope, void *dx, void *dgamma, void *dbeta, float *work, int bf16,
                                         hipStream_t stream);
-int sahs_spade_modulate_bf16_launch(long planes, long hw, const unsigned short *x, const unsigned short *gamma, const unsigned short *beta,
-                                    float eps, float slope, unsigned short *out, float *stats, hipStream_t stream);
-int sahs_spade_modulate_backward_bf16_launch(long planes, long hw, const unsigned short *x, const unsigned short *gamma,
-                                             const unsigned short *out, const float *stats, const unsigned short *grad, float eps, float slope,
-                                             unsigned short *dx, unsigned short *dgamma, unsigned short *dbeta, float *work,
-                                             hipStream_t stream);
 // spectral_norm.hip (the tables as host arrays of device pointers, already validated: capi.hip)
 int sahs_spectral_norm_forward_launch(int jobs, const float *const *W, float *const *u, float *const *v, void *const *out,
                                       float *const *saved, const int *h, const int *w, int out_bf16, int power_iteration, float eps,

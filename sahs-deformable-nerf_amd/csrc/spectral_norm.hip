@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "sahs_common.hpp"
 #include "sahs_launchers.hpp"
-#include "bf16_io.hpp"
+#include "elem_io.hpp"
 #include "../../include/sahs_nerf.h"
 
 namespace sahs {
@@ -25,37 +25,6 @@ struct SnBatch { SnJob j[SN_MAX_JOBS]; };
 struct SnGradJob { const float *W; const float *saved; const void *G; float *dW; int h, w, vec, pad; };
 struct SnGradBatch { SnGradJob j[SN_MAX_JOBS]; };
 static_assert(sizeof(SnBatch) <= 3072 && sizeof(SnGradBatch) <= 3072, "kernel-argument budget");
-
-// group g (N = 1 or a multiple of 4 floats) of the floats at p
-template <int N>
-__device__ __forceinline__ void f32_load(const float *p, long g, float (&v)[N])
-{
-    if constexpr (N == 1) {
-        v[0] = p[g];
-    } else {
-#pragma unroll
-        for (int q = 0; q < N / 4; ++q) {
-            const f32x4 x = reinterpret_cast<const f32x4 *>(p)[g * (N / 4) + q];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[4 * q + k] = x[k];
-        }
-    }
-}
-template <int N>
-__device__ __forceinline__ void f32_store(float *p, long g, const float (&v)[N])
-{
-    if constexpr (N == 1) {
-        p[g] = v[0];
-    } else {
-#pragma unroll
-        for (int q = 0; q < N / 4; ++q) {
-            f32x4 x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x[k] = v[4 * q + k];
-            reinterpret_cast<f32x4 *>(p)[g * (N / 4) + q] = x;
-        }
-    }
-}
 
 __device__ __forceinline__ float wave_sum(float v)
 {
@@ -186,8 +155,7 @@ __device__ __forceinline__ void scale_body(const SnJob &J, float sigma)
         f32_load<N>(J.W, g, a);
 #pragma unroll
         for (int k = 0; k < N; ++k) a[k] = a[k] / sigma;
-        if constexpr (BF16) bf16_store<N>(static_cast<unsigned short *>(J.out), g, a);
-        else f32_store<N>(static_cast<float *>(J.out), g, a);
+        elem_store<N>(static_cast<elem_of<BF16> *>(J.out), g, a);
     }
 }
 // out = W / sigma: grid (chunk, job)
@@ -201,22 +169,17 @@ __global__ void __launch_bounds__(256) spectral_norm_scale_kernel(SnBatch jobs)
 }
 
 template <int N, bool BF16>
-__device__ __forceinline__ void grad_load(const void *G, long g, float (&v)[N])
-{
-    if constexpr (BF16) bf16_load<N>(static_cast<const unsigned short *>(G), g, v);
-    else f32_load<N>(static_cast<const float *>(G), g, v);
-}
-template <int N, bool BF16>
 __device__ __forceinline__ void backward_body(const SnGradJob &J, float *red)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = J.h, w = J.w, ng = w / N;
     const float *su = J.saved, *sv = J.saved + h;
+    const elem_of<BF16> *G = static_cast<const elem_of<BF16> *>(J.G);
     const float sigma = sv[w];
     float acc = 0.0f;
     for (int i = wave; i < h; i += SN_WAVES) {
         for (int g = lane; g < ng; g += 64) {
             float a[N], b[N];
-            grad_load<N, BF16>(J.G, (long)i * ng + g, a);
+            elem_load<N>(G, (long)i * ng + g, a);
             f32_load<N>(J.W, (long)i * ng + g, b);
 #pragma unroll
             for (int k = 0; k < N; ++k) acc += a[k] * b[k];
@@ -227,7 +190,7 @@ __device__ __forceinline__ void backward_body(const SnGradJob &J, float *red)
         const float cu = c * su[i];
         for (int g = lane; g < ng; g += 64) {
             float a[N], b[N];
-            grad_load<N, BF16>(J.G, (long)i * ng + g, a);
+            elem_load<N>(G, (long)i * ng + g, a);
             f32_load<N>(sv, g, b);
 #pragma unroll
             for (int k = 0; k < N; ++k) a[k] = a[k] / sigma - cu * b[k];

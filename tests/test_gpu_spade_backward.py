@@ -1,5 +1,6 @@
-"""The differentiable SPADE modulation on the GPU: the fused backward (csrc/spade_ops.hip: spade_backward_sums_kernel,
-spade_backward_apply_kernel) at op level, through SPADELayer / SPADEBlock, and through one ``refine_step`` of each generator.
+"""The differentiable SPADE modulation on the GPU: the fused backward (csrc/spade_ops.hip: the <float, 4> and <float, 1> instances of
+spade_backward_sums_kernel and spade_backward_apply_kernel) at op level, through SPADELayer / SPADEBlock, and through one
+``refine_step`` of each generator.
 
 The rule everywhere: with E = max |g - g64| / max |g64| against a float64 yardstick (tests/spade_reference.py), the fused path must be
 as close as float32 autograd of the written-out six-op formula ON THE SAME GPU AND INPUTS is -- E_fused <= max(4 * E_unfused, 2^-21).

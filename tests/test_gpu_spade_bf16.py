@@ -1,5 +1,6 @@
-"""The bf16 form of the fused SPADE modulation on the GPU (csrc/spade_ops.hip: instance_stats_bf16_kernel, spade_modulate_bf16_kernel,
-spade_backward_sums_bf16_kernel, spade_backward_apply_bf16_kernel): at op level against a float64 yardstick on the same bf16 values, the
+"""The bf16 form of the fused SPADE modulation on the GPU (csrc/spade_ops.hip: the <unsigned short, 8> and <unsigned short, 1> instances
+of instance_stats_kernel, spade_modulate_kernel, spade_backward_sums_kernel and spade_backward_apply_kernel, the loop bodies the fp32
+instances run): at op level against a float64 yardstick on the same bf16 values, the
 dtype dispatch of ``ops.spade_modulate``, SPADELayer / SPADEBlock and one ``refine_step`` of each generator under
 ``torch.autocast("cuda", dtype=torch.bfloat16)``, and ``G.bfloat16()`` inference.
 

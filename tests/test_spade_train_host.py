@@ -65,6 +65,7 @@ def test_backward_entry_refuses_before_any_launch():
     assert L.sahs_spade_modulate_backward_workspace_words(7) == L.sahs_spade_modulate_workspace_words(7)
     assert call(planes=0) == 0 and call(hw=0) == 0                      # nothing to do: success without a launch
     assert call(planes=65536) == 1 and b"65535" in L.sahs_last_error()      # gridDim.y: the message names the limit
+    assert L.sahs_spade_modulate(65536, 16, A, A, A, 1e-5, 0.2, A, A, None) == 1 and b"65535" in L.sahs_last_error()      # the forward's too
     assert call(planes=-1) == 1 and call(hw=-1) == 1 and call(eps=0.0) == 1
     assert call(out=None) == 1                                          # the mask is read from out unless slope == 1
     assert call(slope=-0.1) == 1 and call(slope=float("nan")) == 1
