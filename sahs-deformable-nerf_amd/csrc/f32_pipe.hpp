@@ -13,25 +13,42 @@ constexpr int F32_THREADS = 512;
 constexpr int F32_PTS_PER_WAVE = 16;
 constexpr int F32_PTS_PER_WG = (F32_THREADS / WAVE) * F32_PTS_PER_WAVE;   // 128
 constexpr int DBG_STRIDE = 56;   // test seam: [dx3, w2, T0[0], trunk layers 1..8 [0], D0[0], D3[0], S0[0], S3[0], pad]
-constexpr int LDS_BUF_FLOATS = CHUNK_FLOATS_MAX;                           // 32 KB each, two of them
-constexpr int LDS_BIAS_OFF = 2 * LDS_BUF_FLOATS;
-constexpr int LDS_FLOATS = LDS_BIAS_OFF + ((BIAS_FLOATS + 3) / 4) * 4;
-static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 
 typedef __attribute__((address_space(3))) void *lds_ptr_t;
 typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
 typedef const __attribute__((address_space(3))) float *lds_cfloat;
 typedef const __attribute__((address_space(3))) f32x4 *lds_cf4;
 
-constexpr int LDS_STASH_OFF = LDS_BIAS_OFF + ((BIAS_FLOATS + 3) / 4) * 4;     // floats
 constexpr int STASH_FLOATS = 8;                                                // per sample: x'[3], w[2] (+pad)
-constexpr int LDS_TOTAL_FLOATS = LDS_STASH_OFF + F32_PTS_PER_WG * STASH_FLOATS;
-static_assert(LDS_TOTAL_FLOATS * 4 <= 160 * 1024, "LDS budget");
 constexpr int PIECE_FLOATS = F32_THREADS * 4;                                  // one DMA piece = 8 KB (1 KB per wave)
-constexpr int MAX_PIECES = LDS_BUF_FLOATS / PIECE_FLOATS;                      // 4
-constexpr int A_AHEAD = 3;                                                     // A fragments (one ds_read_b128 = 4 MFMAs) in flight
+// The chunk cap of a kernel = the size of each of its two LDS staging buffers, in floats.  CHUNK_FLOATS_MAX (32 KB) is what the packed
+// chunk table, the activation-saving forward and the backward chains use; CHUNK_FLOATS_WIDE (64 KB) is the forward without saved
+// activations: half the chunk boundaries of a 256 x 256 layer.  The stream is the same under every cap (sahs_layout.hpp: pick_G).
+constexpr int CHUNK_FLOATS_WIDE = 2 * CHUNK_FLOATS_MAX;
+// The fragment pipeline of a kernel: how many A fragments (one ds_read_b128 = 4 MFMAs) are in flight, and whether every step's order
+// (4 MFMAs, then the read of the fragment a_ahead steps on) is pinned with a scheduling barrier.  Unpinned, the compiler sinks most reads
+// down to their first use (register pressure), and each step then opens with a full LDS round trip that only the SIMD's other wave can
+// cover; the longer the unrolled chunk, the more reads it sinks -- at 64 KB chunks 1,411 of the fine pass's 2,208 reads sat directly in
+// front of their MFMA, and the frame was 5 ms SLOWER than at 32 KB.  Pinned, 4 deep: 12 MFMAs between a read and its use, -12 ms per W512
+// frame (LAB_NOTES.md).  The 32 KB kernels keep their 3 fragments and the compiler's order: their instruction streams are unchanged.
+constexpr int a_ahead(int cap) { return cap > CHUNK_FLOATS_MAX ? 4 : 3; }
+constexpr bool a_pinned(int cap) { return cap > CHUNK_FLOATS_MAX; }
+// LDS of a kernel with cap CAP (floats): [buffer 0][buffer 1][biases][stash][...the kernel's own words]
+template <int CAP>
+struct LdsMap {
+    static constexpr int BUF_FLOATS = CAP;
+    static constexpr int BIAS_OFF = 2 * BUF_FLOATS;
+    static constexpr int STASH_OFF = BIAS_OFF + ((BIAS_FLOATS + 3) / 4) * 4;
+    static constexpr int TOTAL_FLOATS = STASH_OFF + F32_PTS_PER_WG * STASH_FLOATS;
+    static constexpr int MAX_PIECES = BUF_FLOATS / PIECE_FLOATS;               // 4 at 32 KB, 8 at 64 KB
+    static_assert(BUF_FLOATS % PIECE_FLOATS == 0, "a buffer is whole DMA pieces");
+    static_assert(TOTAL_FLOATS * 4 <= 160 * 1024, "LDS budget");
+};
+constexpr int LDS_BUF_FLOATS = LdsMap<CHUNK_FLOATS_MAX>::BUF_FLOATS;           // the 32 KB kernels' (the backward chains size their LDS with these)
+constexpr int MAX_PIECES = LdsMap<CHUNK_FLOATS_MAX>::MAX_PIECES;
 
-struct Ctx {
+template <int CAP>
+struct CtxT {
     const float *stream;      // this level's packed weight stream (global)
     float *lds;               // dynamic LDS base
     int buf;                  // LDS buffer (0/1) holding the current chunk; toggles per chunk (the chunk count is odd, the stream wraps)
@@ -47,7 +64,7 @@ struct Ctx {
     {
         if (off >= wrap_at) off = wrap_to;
         nx_src = reinterpret_cast<const f32x4 *>(stream + off) + lane;
-        nx_dst = reinterpret_cast<f32x4 *>(lds + (buf ^ 1) * LDS_BUF_FLOATS);
+        nx_dst = reinterpret_cast<f32x4 *>(lds + (buf ^ 1) * CAP);
         off += (uint32_t)next_floats;
     }
     __device__ __forceinline__ void issue_piece(int p)   // global_load_lds writes LDS at (wave-uniform base + lane*16)
@@ -68,17 +85,18 @@ struct Ctx {
         }
         buf ^= 1;
     }
-    __device__ __forceinline__ const f32x4 *cur() const { return reinterpret_cast<const f32x4 *>(lds + buf * LDS_BUF_FLOATS); }
+    __device__ __forceinline__ const f32x4 *cur() const { return reinterpret_cast<const f32x4 *>(lds + buf * CAP); }
     // Without the opaque refresh LICM precomputes every tile's bias address outside the persistent loop (~280 VGPRs' worth),
     // spills them, and each reload (a scratch = VMEM op) then waits on vmcnt -- i.e. on the LDS-DMA weight prefetch.
     __device__ __forceinline__ void refresh()
     {
-        uint32_t a = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)lds) + (LDS_BIAS_OFF + 4 * q) * 4;
+        uint32_t a = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)lds) + (LdsMap<CAP>::BIAS_OFF + 4 * q) * 4;
         asm volatile("" : "+v"(a));
         bias_lane = (lds_cfloat)(uintptr_t)a;
     }
     __device__ __forceinline__ f32x4 bias4(int off_) const { return *reinterpret_cast<lds_cf4>(bias_lane + off_); }
 };
+typedef CtxT<CHUNK_FLOATS_MAX> Ctx;
 
 __device__ __forceinline__ f32x4 act4(f32x4 v, float slope)   // slope in [0,1]: leaky relu == max(x, slope*x)
 {
@@ -109,14 +127,15 @@ constexpr int stores_behind_last_piece(int STEPS, int PAIR, int KB, int next_flo
 // two independent accumulation chains alternate (v_mfma_f32_16x16x4_f32: 32-cycle issue, 40-cycle dependent latency).
 // EP: first(cx, out, t) = the accumulator a tile starts from; done<NT>(acc, out, t) = what becomes of the finished tile; EP::kStores = the
 // vector-memory stores done() issues UNCONDITIONALLY per tile (the chunk's closing wait leaves them in flight).
-template <int KB0, int KB1, int NT, int NEXT, class EP>
-__device__ __forceinline__ void dense_ep(Ctx &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, EP &ep)
+template <int KB0, int KB1, int NT, int NEXT, class EP, int CAP>
+__device__ __forceinline__ void dense_ep(CtxT<CAP> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, EP &ep)
 {
     constexpr int KB = KB0 + KB1;
-    constexpr int G = pick_G(KB, NT);
+    constexpr int G = pick_G(KB, NT, CAP);
     constexpr int NCH = NT / G;
     constexpr int PAIR = (G >= 2) ? 2 : 1;             // tiles interleaved
     constexpr int STEPS = G * KB;                      // A fragments per chunk
+    constexpr int A_AHEAD = a_ahead(CAP);
     constexpr int N_MID = stores_behind_last_piece(STEPS, PAIR, KB, G * KB * 256, EP::kStores), N_LAST = stores_behind_last_piece(STEPS, PAIR, KB, NEXT, EP::kStores);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -146,10 +165,11 @@ __device__ __forceinline__ void dense_ep(Ctx &cx, const f32x4 *in0, const f32x4 
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[k], x[k], acc[m], 0, 0, 0);
             if (s + A_AHEAD < STEPS) a[s % A_AHEAD] = A[frag(s + A_AHEAD)];
+            if constexpr (a_pinned(CAP)) __builtin_amdgcn_sched_barrier(0);      // (nothing crosses: the read stays A_AHEAD - 1 steps of MFMAs in front of its use)
             if (b == KB - 1) ep.template done<NT>(acc[m], out, t);
         }
 #pragma unroll
-        for (int pc = (STEPS + pstep - 1) / pstep; pc < MAX_PIECES; ++pc)
+        for (int pc = (STEPS + pstep - 1) / pstep; pc < LdsMap<CAP>::MAX_PIECES; ++pc)
             if (pc < npieces) cx.issue_piece(pc);
         if (c + 1 < NCH) cx.template end_chunk<N_MID>();
         else cx.template end_chunk<N_LAST>();
@@ -164,7 +184,7 @@ struct FwdEp {
     float *save;              // HAS_SAVE: this lane's slot of the layer's saved-activation block (never null: lanes past the end redo the last sample)
     uint32_t *bsave;          // this lane's word(s) of the layer's sign-bit plane (sahs_layout.hpp: sbits), or null
     uint32_t sgn;             // sign nibble of the even tile of a pair, until its odd partner completes the byte
-    __device__ __forceinline__ f32x4 first(const Ctx &cx, const f32x4 *out, int t) const { return accum ? out[t] : cx.bias4(bias_off + 16 * t); }
+    template <class CX> __device__ __forceinline__ f32x4 first(const CX &cx, const f32x4 *out, int t) const { return accum ? out[t] : cx.bias4(bias_off + 16 * t); }
     template <int NT> __device__ __forceinline__ void done(const f32x4 &acc, f32x4 *out, int t)
     {
         f32x4 o = act4(acc, slope);
@@ -181,15 +201,15 @@ struct FwdEp {
     }
 };
 
-template <int KB0, int KB1, int NT, int NEXT>
-__device__ __forceinline__ void dense(Ctx &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, int bias_off, bool accum, float slope)
+template <int KB0, int KB1, int NT, int NEXT, int CAP>
+__device__ __forceinline__ void dense(CtxT<CAP> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, int bias_off, bool accum, float slope)
 {
     FwdEp<false> ep{bias_off, accum, slope, nullptr, nullptr, 0u};
     dense_ep<KB0, KB1, NT, NEXT>(cx, in0, in1, out, ep);
 }
 // SAVING: the launch keeps its activations -- every finished tile also goes to `save` (+ its signs to bsave, where given)
-template <bool SAVING, int KB0, int KB1, int NT, int NEXT>
-__device__ __forceinline__ void dense_sv(Ctx &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, int bias_off, bool accum, float slope,
+template <bool SAVING, int KB0, int KB1, int NT, int NEXT, int CAP>
+__device__ __forceinline__ void dense_sv(CtxT<CAP> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, int bias_off, bool accum, float slope,
                                          float *save, uint32_t *bsave = nullptr)
 {
     FwdEp<SAVING> ep{bias_off, accum, slope, save, SAVING ? bsave : nullptr, 0u};

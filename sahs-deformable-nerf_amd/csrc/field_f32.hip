@@ -14,8 +14,8 @@
 //    features 4q..4q+3 of point j in its 4 registers) is exactly the B operand layout of layer
 //    l+1 (lane (q,j) supplies k = feature 16b+4q+r at step r), so activations stay in VGPRs and
 //    never visit LDS.  f32 MFMA is a k-ordered fmaf chain: results are exact fp32.
-//  * weights are pre-packed in A-fragment order (pack.hip) and streamed L2 -> LDS in <=32 KB
-//    chunks with global_load_lds (no VGPR staging), double buffered, one barrier per chunk; all 8
+//  * weights are pre-packed in A-fragment order (pack.hip) and streamed L2 -> LDS in <=64 KB
+//    chunks (<=32 KB in the activation-saving instances) with global_load_lds (no VGPR staging), double buffered, one barrier per chunk; all 8
 //    waves of the workgroup (2 per SIMD: MFMA of one overlaps VALU/LDS of the other) consume the
 //    same chunk, so each weight byte is fetched once per 128 points.
 //  * persistent workgroups (one per CU) walk 128-point tiles; the weight stream simply wraps.
@@ -134,7 +134,15 @@ __device__ __forceinline__ void trunk_encodings(const float *stash, int q, f32x4
 #endif
 }
 
-#define CHF(id) (kProg.layer[id].G * kProg.layer[id].KB * 256)   /* floats in one chunk of layer id */
+// floats in one chunk of layer id under a chunk cap of `cap` floats (kProg.layer[].G is the 32 KB chunking: pack.hip's table)
+constexpr int chunk_floats(int id, int cap) { return pick_G(kProg.layer[id].KB, kProg.layer[id].NT, cap) * kProg.layer[id].KB * 256; }
+#define CHF(id) chunk_floats(id, CAP)   /* ... of the kernel instance it is used in */
+// The chunk cap of an instance.  Without saved activations: 64 KB buffers, which halve the chunk boundaries of the 256-wide layers (a
+// boundary = MFMA drain + barrier + one LDS round trip with nothing of the next chunk readable), and with them the pinned fragment
+// pipeline of f32_pipe.hpp (a_ahead, a_pinned) -- which is what the 2 % per launch come from; the cap's own share measured 0.4 ms per
+// W512 frame, 11-134 cycles per boundary (LAB_NOTES.md).  The saving instances keep 32 KB and the compiler's order: at 64 KB the
+// whole-network one spills, and their counted closing waits (f32_pipe.hpp: stores_behind_last_piece) are derived for today's chunks.
+constexpr int field_chunk_cap(bool save) { return save ? CHUNK_FLOATS_MAX : CHUNK_FLOATS_WIDE; }
 
 // SAVE: also store every layer's activations (sahs::act layout, 19 KB/sample) for field_bwd.hip
 // MODE: which part of the per-sample network a launch evaluates.  The deformation nets (warp field, hyper sheet) are shared by the
@@ -180,6 +188,10 @@ __host__ __device__ constexpr long sparse_ring_base(long ntiles, long grid, long
     return g * sparse_ring_slots(tlo) + (g < rem ? g : rem) * (sparse_ring_slots(tlo + 1) - sparse_ring_slots(tlo));
 }
 constexpr int LDS_RING_FLOATS = 16;      // fused instances: the waves' live counts of a tile, behind the stash
+constexpr bool field_mode_fused(int mode) { return mode == 6 || mode == 7; }      // (FIELD_ALL_FUSED, FIELD_RADIANCE_FUSED)
+// dynamic LDS of an instance: two chunk buffers of its cap, biases, stash (+ ring words)
+constexpr int field_lds_floats(bool save, int mode) { return (save ? LdsMap<field_chunk_cap(true)>::TOTAL_FLOATS : LdsMap<field_chunk_cap(false)>::TOTAL_FLOATS) + (field_mode_fused(mode) ? LDS_RING_FLOATS : 0); }
+static_assert(field_lds_floats(false, 7) * 4 <= 160 * 1024 && field_lds_floats(true, 0) * 4 <= 160 * 1024, "LDS budget of the largest instance of each cap");
 // The record workspace of the fused instances (the kernel's argument block; the launcher fills it from one allocation).  Records sit in
 // groups of 16 slots (one wave of a branch pass); a group's feat is laid out [k-block 16][lane 64][4] like a weight fragment, so a branch
 // pass loads it with whole 1-KB wave transactions.
@@ -205,8 +217,10 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
     constexpr bool FUSED = MODE == FIELD_ALL_FUSED || MODE == FIELD_RADIANCE_FUSED;      // sparse branches: trunk, ring append and branch pass in one launch
     constexpr bool XW_IN = MODE == FIELD_RADIANCE || MODE == FIELD_RADIANCE_FUSED;       // x', w come from xw through src
     static_assert(!(SAVE && FUSED), "the sparse branches are an inference path");
+    constexpr int CAP = field_chunk_cap(SAVE);
+    typedef LdsMap<CAP> Lds;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    Ctx cx;
+    CtxT<CAP> cx;
     cx.stream = packed + PACK_STREAM_OFF + (long)level * STREAM_FLOATS;
     cx.lds = lds;
     cx.buf = 1;                       // so that the first chunk lands in buffer 0
@@ -222,7 +236,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
 
     {   // per-level biases (static + folded conditioning) -> LDS, first weight chunk -> buffer 0
         const float *bsrc = frame + FRAME_BIAS_OFF + level * BIAS_FLOATS;
-        for (int i = threadIdx.x; i < BIAS_FLOATS; i += F32_THREADS) lds[LDS_BIAS_OFF + i] = bsrc[i];
+        for (int i = threadIdx.x; i < BIAS_FLOATS; i += F32_THREADS) lds[Lds::BIAS_OFF + i] = bsrc[i];
         cx.begin_chunk(CHF(L_START));
 #pragma unroll
         for (int pc = 0; pc < (CHF(L_START) + PIECE_FLOATS - 1) / PIECE_FLOATS; ++pc) cx.issue_piece(pc);
@@ -281,15 +295,16 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         cx.refresh();
         // (a tile of the 4-layer-trunk models that stops behind fc_alpha has no rolled layer loop, so the stream offset of every chunk is the same constant
         // in every tile and LICM precomputes all ~100 LDS-DMA source addresses outside the persistent loop -- a kilobyte of scratch per
-        // lane -- unless the offset is opaque per tile; likewise the encodings' per-lane octave selectors and the lane quarter)
+        // lane -- unless the offset is opaque per tile; likewise the encodings' per-lane octave selectors and the lane quarter.  At the 64 KB
+        // cap the dense instances of those models need the same: without it NeRFaceModel's <false,0> and <false,2> sit at 256 registers and spill)
         int q_tile = cx.q;
-        if constexpr (FUSED) { asm volatile("" : "+s"(cx.off)); asm volatile("" : "+v"(q_tile)); }
+        if constexpr (FUSED || (!SAVE && TR_LAYERS == 4)) { asm volatile("" : "+s"(cx.off)); asm volatile("" : "+v"(q_tile)); }
         const int q = q_tile;
         const long p_raw = tile * F32_PTS_PER_WG + cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15);
         const long p = p_raw < P ? p_raw : P - 1;
         // x' (3) and w (2) are parked in LDS between their uses; the ray direction is re-read where needed: values that stay
         // live across the 256-wide layers get spilled to scratch, and a scratch reload drains the LDS-DMA prefetch (vmcnt).
-        float *stash = lds + LDS_STASH_OFF + (cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15)) * STASH_FLOATS;
+        float *stash = lds + Lds::STASH_OFF + (cx.wave * F32_PTS_PER_WAVE + (cx.lane & 15)) * STASH_FLOATS;
         const bool dump = MODE == FIELD_ALL && dbg != nullptr && q == 0 && p_raw < P;   // lanes holding feature 0 of tile 0
         float *dsl = dbg + p * DBG_STRIDE;
         // saved activations are one dense [P x width] array per layer (array at column c of the act:: table starts at c * P):
@@ -372,7 +387,8 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
         {
             f32x4 h[8], hn[8];
             dense_sv<SAVE, KB_XYZ, 0, 8, CHF(L_W1)>(cx, pe_x, nullptr, h, Ly[L_W0].bias_off, false, 0.0f, SV(act::WH, 128), SBD(sbits::BD_WH + 4 * (0), 128));
-            // W1..W3; the chunk after each is W2, W3, W4B.  One rolled loop where those have the same size (AudioFaceModel: 32 KB)
+            // W1..W3; the chunk after each is W2, W3, W4B.  One rolled loop where those have the same size (AudioFaceModel at the 32 KB cap; at 64 KB a
+            // 128 x 128 layer is one 64 KB chunk, W4B's stays 32 KB, and W3 is spelled out)
             constexpr int W_ROLLED = (CHF(L_W4B) == CHF(L_W2)) ? 3 : 2;
 #pragma unroll 1
             for (int l = 0; l < W_ROLLED; ++l) {
@@ -506,7 +522,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             for (int i = 0; i < 16; ++i) h[i] = feat[i];
 #if SAHS_MODEL == 0
 #pragma unroll 1
-            for (int l = 4; l <= 7; ++l) {     // T4..T7 (next chunks: T5, T6, T7, FEAT, all 32 KB)
+            for (int l = 4; l <= 7; ++l) {     // T4..T7 (next chunks: T5, T6, T7, FEAT, all of one size: the cap)
                 dense_sv<SAVE, 16, 0, 16, CHF(L_T5)>(cx, h, nullptr, feat, Ly[L_T4].bias_off + 256 * (l - 4), false, 0.01f, SV(act::T + 256 * l, 256), SBR(sbits::BR_T + 8 * (l), 256));
                 if (dump) dsl[5 + l] = feat[0][0];
 #pragma unroll
@@ -534,7 +550,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
                 const bool live = q == 3 && p_raw < P && (last ? sp.has_bg == 0 : sg > 0.0f);
                 const uint32_t mask = (uint32_t)(__ballot(live) >> 48);      // bit j: column j of this wave's 16 samples
                 // slots: the waves' live counts through LDS (read again only after the many chunk barriers of the next tile)
-                uint32_t *cnts = reinterpret_cast<uint32_t *>(lds + LDS_TOTAL_FLOATS);
+                uint32_t *cnts = reinterpret_cast<uint32_t *>(lds + Lds::TOTAL_FLOATS);
                 if (cx.lane == 0) cnts[cx.wave] = (uint32_t)__popc(mask);
                 __syncthreads();
                 uint32_t before = 0u, all = 0u;
@@ -644,7 +660,7 @@ using namespace SAHS_NS;
 template <bool SAVE, int MODE>
 static int launch_field(const FieldLaunch &L, SparseArgs sp = SparseArgs{})
 {
-    const size_t lds_bytes = (size_t)(LDS_TOTAL_FLOATS + ((MODE == FIELD_ALL_FUSED || MODE == FIELD_RADIANCE_FUSED) ? LDS_RING_FLOATS : 0)) * sizeof(float);
+    const size_t lds_bytes = (size_t)field_lds_floats(SAVE, MODE) * sizeof(float);
     return sahs_launch_persistent<field_forward_f32_kernel<SAVE, MODE>>((L.P + F32_PTS_PER_WG - 1) / F32_PTS_PER_WG, L.num_cu, F32_THREADS, lds_bytes, L.stream,
                                                                         L.packed, L.frame, L.level, L.P, L.S, L.rays, L.ray_stride, L.zvals, L.raw, L.dbg,
                                                                         L.actbuf, L.xw, L.xw_row, L.xw_col0, L.src, L.bits, sp);

@@ -161,13 +161,16 @@ struct Layer {
 };
 
 constexpr int CHUNK_FLOATS_MAX = 8192;   // 32 KB LDS staging buffer
-constexpr int pick_G(int KB, int NT)
+// Tiles per chunk under a cap of `cap` floats.  A chunking is a schedule, not a layout: the stream is [tile][k-block][lane][4] whatever G is,
+// so kernels with different caps walk the same packed weights.  Layer::G and the packed chunk table are the 32 KB chunking.
+constexpr int pick_G(int KB, int NT, int cap)
 {
-    int g = CHUNK_FLOATS_MAX / (KB * 256);
+    int g = cap / (KB * 256);
     if (g > NT) g = NT;
     while (NT % g) --g;   // largest divisor of NT not above g
     return g;
 }
+constexpr int pick_G(int KB, int NT) { return pick_G(KB, NT, CHUNK_FLOATS_MAX); }
 
 struct Program {
     Layer layer[NUM_LAYERS];
