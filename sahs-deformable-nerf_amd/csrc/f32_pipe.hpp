@@ -33,6 +33,13 @@ constexpr int CHUNK_FLOATS_WIDE = 2 * CHUNK_FLOATS_MAX;
 // frame (LAB_NOTES.md).  The 32 KB kernels keep their 3 fragments and the compiler's order: their instruction streams are unchanged.
 constexpr int a_ahead(int cap) { return cap > CHUNK_FLOATS_MAX ? 4 : 3; }
 constexpr bool a_pinned(int cap) { return cap > CHUNK_FLOATS_MAX; }
+// The tile starts of a pinned kernel (BIAS_AHEAD of its context; false = the step as it was).  Pinned, a step's order is the source's, and
+// the source had a tile open with its bias read: a ds_read_b128 directly in front of the tile's first MFMA, and, lgkmcnt retiring in order,
+// the wait for it also drained the fragment read issued just before, 12 MFMAs early for nothing.  With BIAS_AHEAD the bias fragment of the
+// tile that next starts in slot m is read a_ahead steps before its first MFMA, in front of that step's scheduling barrier, into a ring of
+// PAIR register quadruples (the MFMA takes it as srcC: no copy); the ring lives across a layer's chunks, and a layer's first pair reads
+// both of its fragments in front of the chunk's first weight fragments -- the one exposed round trip a layer keeps.  -5.0 ms per W512
+// frame.  (Moving a finished tile's activation behind the MFMAs of the following step as well did not pay: LAB_NOTES.md.)
 // LDS of a kernel with cap CAP (floats): [buffer 0][buffer 1][biases][stash][...the kernel's own words]
 template <int CAP>
 struct LdsMap {
@@ -47,7 +54,7 @@ struct LdsMap {
 constexpr int LDS_BUF_FLOATS = LdsMap<CHUNK_FLOATS_MAX>::BUF_FLOATS;           // the 32 KB kernels' (the backward chains size their LDS with these)
 constexpr int MAX_PIECES = LdsMap<CHUNK_FLOATS_MAX>::MAX_PIECES;
 
-template <int CAP>
+template <int CAP, bool BIAS_AHEAD = false>
 struct CtxT {
     const float *stream;      // this level's packed weight stream (global)
     float *lds;               // dynamic LDS base
@@ -127,8 +134,8 @@ constexpr int stores_behind_last_piece(int STEPS, int PAIR, int KB, int next_flo
 // two independent accumulation chains alternate (v_mfma_f32_16x16x4_f32: 32-cycle issue, 40-cycle dependent latency).
 // EP: first(cx, out, t) = the accumulator a tile starts from; done<NT>(acc, out, t) = what becomes of the finished tile; EP::kStores = the
 // vector-memory stores done() issues UNCONDITIONALLY per tile (the chunk's closing wait leaves them in flight).
-template <int KB0, int KB1, int NT, int NEXT, class EP, int CAP>
-__device__ __forceinline__ void dense_ep(CtxT<CAP> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, EP &ep)
+template <int KB0, int KB1, int NT, int NEXT, class EP, int CAP, bool BIAS_RING>
+__device__ __forceinline__ void dense_ep(CtxT<CAP, BIAS_RING> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, EP &ep)
 {
     constexpr int KB = KB0 + KB1;
     constexpr int G = pick_G(KB, NT, CAP);
@@ -136,6 +143,9 @@ __device__ __forceinline__ void dense_ep(CtxT<CAP> &cx, const f32x4 *in0, const 
     constexpr int PAIR = (G >= 2) ? 2 : 1;             // tiles interleaved
     constexpr int STEPS = G * KB;                      // A fragments per chunk
     constexpr int A_AHEAD = a_ahead(CAP);
+    // (the ring: a slot is read again a_ahead steps before its tile starts, so its previous tile must have started by then)
+    constexpr bool BIAS_AHEAD = a_pinned(CAP) && BIAS_RING && PAIR * KB > A_AHEAD;
+    f32x4 bias[PAIR];      // BIAS_AHEAD: what the tile that next starts in slot m starts from (lives across the layer's chunks)
     constexpr int N_MID = stores_behind_last_piece(STEPS, PAIR, KB, G * KB * 256, EP::kStores), N_LAST = stores_behind_last_piece(STEPS, PAIR, KB, NEXT, EP::kStores);
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -148,6 +158,12 @@ __device__ __forceinline__ void dense_ep(CtxT<CAP> &cx, const f32x4 *in0, const 
         // step s -> (pair p, block b, member m): order p-major, then b, then m
         auto frag = [&](int s) { const int pp = s / (PAIR * KB), r = s % (PAIR * KB); return ((pp * PAIR + r % PAIR) * KB + r / PAIR) * 64; };
         f32x4 a[A_AHEAD];
+        if constexpr (BIAS_AHEAD) {      // the layer's first pair: in front of the chunk's first fragments, one round trip for all of them
+            if (c == 0 && ep.reads_bias()) {
+#pragma unroll
+                for (int m = 0; m < PAIR; ++m) bias[m] = ep.ahead(cx, m);
+            }
+        }
 #pragma unroll
         for (int s = 0; s < A_AHEAD && s < STEPS; ++s) a[s] = A[frag(s)];
         f32x4 acc[PAIR];
@@ -155,7 +171,10 @@ __device__ __forceinline__ void dense_ep(CtxT<CAP> &cx, const f32x4 *in0, const 
         for (int s = 0; s < STEPS; ++s) {
             const int pp = s / (PAIR * KB), r = s % (PAIR * KB), m = r % PAIR, b = r / PAIR;
             const int t = c * G + pp * PAIR + m;
-            if (b == 0) acc[m] = ep.first(cx, out, t);
+            if (b == 0) {
+                if constexpr (BIAS_AHEAD) acc[m] = ep.first_from(bias[m], out, t);
+                else acc[m] = ep.first(cx, out, t);
+            }
             if (s % pstep == 0 && s / pstep < npieces) {
                 cx.issue_piece(s / pstep);
                 if (EP::kStores > 0 && s / pstep == npieces - 1) __builtin_amdgcn_sched_barrier(0);      // (the counted wait below: no store moves in front of the last piece)
@@ -164,6 +183,13 @@ __device__ __forceinline__ void dense_ep(CtxT<CAP> &cx, const f32x4 *in0, const 
             const f32x4 w = a[s % A_AHEAD];
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[k], x[k], acc[m], 0, 0, 0);
+            if constexpr (BIAS_AHEAD) {      // step u = s + A_AHEAD opens a tile (of a later pair of this chunk, or of the next chunk's first pair)
+                const int u = s + A_AHEAD;
+                if (ep.reads_bias()) {
+                    if (u < STEPS) { if (u >= PAIR * KB && u % (PAIR * KB) < PAIR) bias[u % PAIR] = ep.ahead(cx, c * G + (u / (PAIR * KB)) * PAIR + u % PAIR); }
+                    else if (c + 1 < NCH && u - STEPS < PAIR) bias[u - STEPS] = ep.ahead(cx, (c + 1) * G + (u - STEPS));
+                }
+            }
             if (s + A_AHEAD < STEPS) a[s % A_AHEAD] = A[frag(s + A_AHEAD)];
             if constexpr (a_pinned(CAP)) __builtin_amdgcn_sched_barrier(0);      // (nothing crosses: the read stays A_AHEAD - 1 steps of MFMAs in front of its use)
             if (b == KB - 1) ep.template done<NT>(acc[m], out, t);
@@ -185,6 +211,10 @@ struct FwdEp {
     uint32_t *bsave;          // this lane's word(s) of the layer's sign-bit plane (sahs_layout.hpp: sbits), or null
     uint32_t sgn;             // sign nibble of the even tile of a pair, until its odd partner completes the byte
     template <class CX> __device__ __forceinline__ f32x4 first(const CX &cx, const f32x4 *out, int t) const { return accum ? out[t] : cx.bias4(bias_off + 16 * t); }
+    // first() in two halves (BIAS_AHEAD): the LDS read of tile t's bias, issued steps ahead, and the choice at the tile's start
+    __device__ __forceinline__ bool reads_bias() const { return !accum; }
+    template <class CX> __device__ __forceinline__ f32x4 ahead(const CX &cx, int t) const { return cx.bias4(bias_off + 16 * t); }
+    __device__ __forceinline__ f32x4 first_from(const f32x4 &b, const f32x4 *out, int t) const { return accum ? out[t] : b; }
     template <int NT> __device__ __forceinline__ void done(const f32x4 &acc, f32x4 *out, int t)
     {
         f32x4 o = act4(acc, slope);
@@ -201,15 +231,15 @@ struct FwdEp {
     }
 };
 
-template <int KB0, int KB1, int NT, int NEXT, int CAP>
-__device__ __forceinline__ void dense(CtxT<CAP> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, int bias_off, bool accum, float slope)
+template <int KB0, int KB1, int NT, int NEXT, int CAP, bool BIAS_RING>
+__device__ __forceinline__ void dense(CtxT<CAP, BIAS_RING> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, int bias_off, bool accum, float slope)
 {
     FwdEp<false> ep{bias_off, accum, slope, nullptr, nullptr, 0u};
     dense_ep<KB0, KB1, NT, NEXT>(cx, in0, in1, out, ep);
 }
 // SAVING: the launch keeps its activations -- every finished tile also goes to `save` (+ its signs to bsave, where given)
-template <bool SAVING, int KB0, int KB1, int NT, int NEXT, int CAP>
-__device__ __forceinline__ void dense_sv(CtxT<CAP> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, int bias_off, bool accum, float slope,
+template <bool SAVING, int KB0, int KB1, int NT, int NEXT, int CAP, bool BIAS_RING>
+__device__ __forceinline__ void dense_sv(CtxT<CAP, BIAS_RING> &cx, const f32x4 *in0, const f32x4 *in1, f32x4 *out, int bias_off, bool accum, float slope,
                                          float *save, uint32_t *bsave = nullptr)
 {
     FwdEp<SAVING> ep{bias_off, accum, slope, save, SAVING ? bsave : nullptr, 0u};

@@ -143,6 +143,18 @@ constexpr int chunk_floats(int id, int cap) { return pick_G(kProg.layer[id].KB, 
 // W512 frame, 11-134 cycles per boundary (LAB_NOTES.md).  The saving instances keep 32 KB and the compiler's order: at 64 KB the
 // whole-network one spills, and their counted closing waits (f32_pipe.hpp: stores_behind_last_piece) are derived for today's chunks.
 constexpr int field_chunk_cap(bool save) { return save ? CHUNK_FLOATS_MAX : CHUNK_FLOATS_WIDE; }
+// Whether an instance reads its tiles' biases ahead (f32_pipe.hpp: BIAS_AHEAD): the pinned ones, i.e. those without saved activations; the
+// saving instances keep the step as it was.  SAHS_F32_BIAS_AHEAD / SAHS_F32_ENC_ONCE6: pricing builds (tools/ablate.py), one part at a time.
+#if defined(SAHS_DIAG) && defined(SAHS_F32_BIAS_AHEAD)
+constexpr bool field_bias_ahead(bool save) { return !save && (SAHS_F32_BIAS_AHEAD) != 0; }
+#else
+constexpr bool field_bias_ahead(bool save) { return !save; }
+#endif
+#if defined(SAHS_DIAG) && defined(SAHS_F32_ENC_ONCE6)
+constexpr bool field_enc_once6() { return (SAHS_F32_ENC_ONCE6) != 0; }
+#else
+constexpr bool field_enc_once6() { return true; }
+#endif
 
 // SAVE: also store every layer's activations (sahs::act layout, 19 KB/sample) for field_bwd.hip
 // MODE: which part of the per-sample network a launch evaluates.  The deformation nets (warp field, hyper sheet) are shared by the
@@ -220,7 +232,7 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
     constexpr int CAP = field_chunk_cap(SAVE);
     typedef LdsMap<CAP> Lds;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    CtxT<CAP> cx;
+    CtxT<CAP, field_bias_ahead(SAVE)> cx;
     cx.stream = packed + PACK_STREAM_OFF + (long)level * STREAM_FLOATS;
     cx.lds = lds;
     cx.buf = 1;                       // so that the first chunk lands in buffer 0
@@ -460,11 +472,11 @@ field_forward_f32_kernel(const float *__restrict__ packed, const float *__restri
             f32x4 h[16];
             if constexpr (FUSED) {      // (T0..T3A spelled apart from the dense instances' below: one body for both compiles the dense ones differently)
                 // PE(x'), PE(w) feed T0 and, re-injected, the skip layer T3A.  The trunk part of a fused tile holds no ray direction or grid
-                // blocks, so in the fine pass the 24 registers can stay live through T1, T2 and the encodings be built once per tile (a build
-                // is ~1,000 VALU instructions per wave, and all eight waves run it at the same moment, the matrix pipe idle).  Measured per
-                // launch (W512 frame, LAB_NOTES.md): -1.3 % for the fine trunk; for FIELD_ALL_FUSED, whose tile also runs the deformation
-                // nets, the -0.8 % is below that launch's own spread, and it keeps the rebuild like the dense instances.
-                constexpr bool ENC_ONCE = MODE == FIELD_RADIANCE_FUSED;
+                // blocks, so the 24 registers can stay live through T1, T2 and the encodings be built once per tile (a build is ~1,000 VALU
+                // instructions per wave, and all eight waves run it at the same moment, the matrix pipe idle).  Measured (W512 frame,
+                // LAB_NOTES.md): -1.3 % of the launch for the fine trunk; for FIELD_ALL_FUSED, whose tile also runs the deformation nets,
+                // -0.8 % of its trunk was below that launch's own spread, but on the frame it is -3.0 ms, apart from the parent's series.
+                constexpr bool ENC_ONCE = MODE == FIELD_RADIANCE_FUSED || field_enc_once6();
                 f32x4 in_tr[KB_XYZ + KB_AMB];
                 auto build_enc = [&]() { trunk_encodings(stash, q, in_tr); };
                 build_enc();

@@ -22,6 +22,12 @@ VARIANTS = {"base": ["SAHS_DIAG"],
             "x3floor": ["SAHS_DIAG", "SAHS_X3_NODMA", "SAHS_X3_NOBARRIER", "SAHS_X3_NOAREAD"],
             # the backward chain kernels (csrc/field_bwd_chain.hip): what they wait for (tools/ab_chain.sh runs them under rocprofv3)
             "cnostore": ["SAHS_DIAG", "SAHS_BWC_NOSTORE"], "cnogstore": ["SAHS_DIAG", "SAHS_BWC_NOGSTORE"], "ctilemajor": ["SAHS_DIAG", "SAHS_BWC_TILEMAJOR"], "cplainstore": ["SAHS_DIAG", "SAHS_BWC_PLAINSTORE"],
+            # the fp32 forward's tile starts and the fused coarse tile's encodings (csrc/field_f32.hip: field_bias_ahead, field_enc_once6), one
+            # part at a time -- pricing builds with RIGHT results (a schedule each), run through bench.py with SAHS_NERF_LIB; f32_edges_none
+            # is the kernel as it was (same ISA as the commit before them: tools/compare_isa.py)
+            "f32_edges_none": ["SAHS_DIAG", "SAHS_F32_BIAS_AHEAD=0", "SAHS_F32_ENC_ONCE6=0"],
+            "f32_bias_ahead": ["SAHS_DIAG", "SAHS_F32_BIAS_AHEAD=1", "SAHS_F32_ENC_ONCE6=0"],
+            "f32_enc_once6": ["SAHS_DIAG", "SAHS_F32_BIAS_AHEAD=0", "SAHS_F32_ENC_ONCE6=1"],
             "cnomask": ["SAHS_DIAG", "SAHS_BWC_NOMASK"], "cnostore_nomask": ["SAHS_DIAG", "SAHS_BWC_NOSTORE", "SAHS_BWC_NOMASK"]}
 
 
