@@ -486,6 +486,43 @@ size_t sahs_lpips_distance_workspace_bytes(int jobs, long B, const long *hw);
 int sahs_lpips_distance(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
                         double *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- frame products: the bytes Stage-I evaluation writes for a rendered frame, fused (the reference's eval_stage_rays.py tail: image
+ * and disparity casts, torch_normal_map, nerf/utils.py label2color) ----
+ * For B frames of H x W pixels.  Inputs (device pointers):
+ *   rgb    fp32, C = 3 or C = 15 channels per pixel ([rgb3 | seg12], as the renderer emits it), addressed by three ELEMENT strides
+ *          stride_rgb[0..2] = (batch, row, column), a host array read before the call returns; the channel stride is 1.  The (H W, 15)
+ *          render output, its [..., :3] view and a stacked (B, H, W, 15) are read in place.  May be null when neither image nor seg is asked for.
+ *   disp   fp32 (B, H, W) contiguous, or null.     w_bg  fp32 (B, H, W) contiguous, or null; read only when clean != 0.
+ *   intrinsics  HOST array [fx, fy, cx, cy], cx and cy as fractions of the width and the height, or null.
+ * Outputs (device pointers, each contiguous, each optional: null = not asked for):
+ *   image       u8 (B, H, W, 3): clamp(x, 0, 1) * 255 in fp32, truncated.
+ *   seg         u8 (B, H, W, 3): the colour of the arg-max of the 12 scores rgb[..., 3:15]; the first maximum wins and a NaN counts as
+ *               the maximum (numpy's argmax).  Needs C = 15.
+ *   normals_u8  u8 (B, H - d, W - d, 3) and / or normals_f32, fp32 of the same shape; d = 2 with central_difference, else 1.  With
+ *               p(r, c) = [((c - cx W) t) / fx, -((r - cy H) t) / fy, t], t = disp[r][c]:  n = cross(p(r, c + d) - p(r, c), p(r + d, c) - p(r, c)),
+ *               v = (n / |n|) * 0.5 + 0.5; with clean != 0 and w_bg given, m = w_bg[r][c]: v = 1 where m > 0.22, then v = (1 - m) v + m;
+ *               normals_f32 = v * 255 (not clamped), normals_u8 = clamp(v * 255, 0, 255) truncated.  RECTANGULAR maps: the column index
+ *               enters x with cx * W and the row index enters y with cy * H; for square maps this is the reference's function.
+ *               H <= d or W <= d: the plane is empty and nothing is written to it.  Needs disp and intrinsics.
+ *   disparity   u8 (B, H, W): (t - min) / (max - min) with min and max PER FRAME, an fp32 subtraction and a correctly rounded fp32
+ *               division, then clamp(., 0, 1) * 255 truncated.  Needs disp.
+ * Every step is one correctly rounded fp32 operation in the order written above.
+ * NaN rule: any NaN that reaches a byte conversion is stored as 0, in every plane.  min and max propagate NaN: a frame whose disparity
+ * holds a NaN gets an all-zero disparity plane (the other frames of the batch are not affected), and so does a constant frame (0 / 0).
+ * workspace: sahs_frame_products_workspace_bytes(B, H, W) bytes, 16-byte aligned (one record of 16 bytes per frame and tile of
+ * SAHS_FRAME_PRODUCTS_TILE^2 pixels); 0 from the query means the shape is invalid (or B == 0).  Needed only with disparity.
+ * At most two launches whatever B is, no atomics: bit-reproducible, and a batch gives the bits of its single calls.
+ * Invalid, refused with a message that names it before any HIP call: H or W outside 1 .. 32768; B < 0 (B == 0 succeeds without a
+ * launch) or B * tiles >= 2^31; C other than 3 or 15; seg with C = 3; normals without disp and intrinsics; disparity without disp;
+ * image or seg without rgb or stride_rgb; a negative stride; intrinsics with fx or fy zero or not finite; a pointer not aligned to its
+ * element (workspace: 16 bytes); workspace_bytes below the query's value when disparity is asked for. */
+#define SAHS_FRAME_PRODUCTS_TILE 32
+size_t sahs_frame_products_workspace_bytes(long B, int H, int W);
+int sahs_frame_products(const float *rgb, int C, const long *stride_rgb, const float *disp, const float *w_bg, const float *intrinsics,
+                        long B, int H, int W, int clean, int central_difference, unsigned char *image, unsigned char *seg,
+                        unsigned char *normals_u8, float *normals_f32, unsigned char *disparity, void *workspace, size_t workspace_bytes,
+                        void *stream);
+
 /* ---- launch probe (opt-in measurement aid; the one exception to "never synchronises") ----
  * While armed on the calling thread, every FIELD-kernel launch the library makes (from any entry point above) is bracketed by two HIP
  * events recorded on the launch stream, up to `capacity` launches (further ones are counted as dropped and run unprobed).

@@ -409,6 +409,63 @@ int sahs_image_metrics(const void *a, const void *b, int dtype, long B, int H, i
     return e ? hip_fail(who, e) : 0;
 }
 
+// frame products: every refusal names what it refuses, before any HIP call
+static bool frame_products_shape(long B, int H, int W)
+{
+    return B >= 0 && H >= 1 && W >= 1 && H <= 32768 && W <= 32768 && B * sahs_frame_products_tiles(H, W) < 2147483648L;
+}
+
+size_t sahs_frame_products_workspace_bytes(long B, int H, int W)
+{
+    return frame_products_shape(B, H, W) ? (size_t)B * (size_t)sahs_frame_products_tiles(H, W) * 16u : 0;
+}
+
+int sahs_frame_products(const float *rgb, int C, const long *stride_rgb, const float *disp, const float *w_bg, const float *intrinsics,
+                        long B, int H, int W, int clean, int central_difference, unsigned char *image, unsigned char *seg,
+                        unsigned char *normals_u8, float *normals_f32, unsigned char *disparity, void *workspace, size_t workspace_bytes,
+                        void *stream)
+{
+    const char *who = "sahs_frame_products";
+    if (H < 1 || W < 1 || H > 32768 || W > 32768)
+        return fail(1, "%s: frames of %d x %d pixels, needs 1 <= H, W <= 32768 (capi.hip:%d)", who, H, W, __LINE__);
+    if (C != 3 && C != 15)
+        return fail(1, "%s: C = %d channels, must be 3 (rgb) or 15 (rgb and the 12 class scores) (capi.hip:%d)", who, C, __LINE__);
+    if (!frame_products_shape(B, H, W))
+        return fail(1, "%s: B = %ld frames, needs B >= 0 and B * tiles < 2^31 (capi.hip:%d)", who, B, __LINE__);
+    if (seg && C != 15)
+        return fail(1, "%s: seg asked for with C = 3: the mask colours need the 12 class scores, C = 15 (capi.hip:%d)", who, __LINE__);
+    if ((normals_u8 || normals_f32) && (!disp || !intrinsics))
+        return fail(1, "%s: normals asked for without %s: the normal map needs disp and the intrinsics [fx, fy, cx, cy] (capi.hip:%d)", who,
+                    !disp ? "disp" : "intrinsics", __LINE__);
+    if (disparity && !disp) return fail(1, "%s: disparity asked for without disp (capi.hip:%d)", who, __LINE__);
+    if ((image || seg) && (!rgb || !stride_rgb))
+        return fail(1, "%s: image or seg asked for with a null %s (capi.hip:%d)", who, !rgb ? "rgb" : "stride_rgb", __LINE__);
+    if (stride_rgb)
+        for (int k = 0; k < 3; ++k)
+            if (stride_rgb[k] < 0) return fail(1, "%s: stride %d is negative (%ld) (capi.hip:%d)", who, k, stride_rgb[k], __LINE__);
+    if (intrinsics && (!std::isfinite(intrinsics[0]) || !std::isfinite(intrinsics[1]) || intrinsics[0] == 0.0f || intrinsics[1] == 0.0f))
+        return fail(1, "%s: intrinsics fx = %g, fy = %g, must be finite and not 0 (capi.hip:%d)", who, (double)intrinsics[0],
+                    (double)intrinsics[1], __LINE__);
+    if (B == 0) return 0;
+    if (((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(disp) | reinterpret_cast<uintptr_t>(w_bg) |
+          reinterpret_cast<uintptr_t>(normals_f32)) & 3u) != 0)
+        return fail(1, "%s: rgb, disp, w_bg and normals_f32 must be aligned to their 4-byte elements (capi.hip:%d)", who, __LINE__);
+    if (disparity) {
+        if (!workspace) return fail(1, "%s: null pointer for workspace (disparity asked for) (capi.hip:%d)", who, __LINE__);
+        if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return fail(1, "%s: workspace must be 16-byte aligned (capi.hip:%d)", who, __LINE__);
+        const size_t need = sahs_frame_products_workspace_bytes(B, H, W);
+        if (workspace_bytes < need)
+            return fail(1, "%s: workspace of %zu bytes, needs %zu (sahs_frame_products_workspace_bytes) (capi.hip:%d)", who, workspace_bytes, need,
+                        __LINE__);
+    }
+    const int d = central_difference ? 2 : 1;
+    if (H <= d || W <= d) { normals_u8 = nullptr; normals_f32 = nullptr; }      // an empty plane: nothing to write
+    if (!image && !seg && !normals_u8 && !normals_f32 && !disparity) return 0;
+    int e = sahs_frame_products_launch(rgb, C, stride_rgb, disp, clean ? w_bg : nullptr, intrinsics, B, H, W, clean, central_difference, image, seg,
+                                       normals_u8, normals_f32, disparity, workspace, (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
 // LPIPS, the scaling layer and the distance head: every refusal names what it refuses, before any HIP call
 int sahs_lpips_prepare(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
                        int normalize, float *out, void *stream)

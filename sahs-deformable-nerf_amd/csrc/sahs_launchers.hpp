@@ -77,6 +77,11 @@ int sahs_lpips_prepare_launch(const void *a, const void *b, int is_float, long B
 long sahs_lpips_distance_tiles(int jobs, const long *hw);
 int sahs_lpips_distance_launch(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
                                double *out, double *records, hipStream_t stream);
+// frame_products.hip (arguments already validated: capi.hip; records: B * sahs_frame_products_tiles(H, W) * 16 bytes, with disparity)
+long sahs_frame_products_tiles(int H, int W);
+int sahs_frame_products_launch(const float *rgb, int C, const long *stride_rgb, const float *disp, const float *w_bg, const float *intrinsics,
+                               long B, int H, int W, int clean, int central_difference, uint8_t *image, uint8_t *seg, uint8_t *normals_u8,
+                               float *normals_f32, uint8_t *disparity, void *records, hipStream_t stream);
 // optim.hip (w1 =1 - beta1, w2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): formed in double by the caller)
 int sahs_adam_step_launch(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float w1, float beta2, float w2,
                           float step_size, float bc2_sqrt, float eps, float grad_scale, hipStream_t stream);

@@ -11,6 +11,7 @@ import time
 import numpy as np
 import torch
 
+from . import ops
 from .nerf_helpers import get_ray_bundle
 from .train_utils import partition_invariant_rng, run_one_iter_of_nerf
 
@@ -79,14 +80,18 @@ def _save_png(path, arr):
     Image.fromarray(arr).save(path)
 
 
-def render_frames(model, cfg, frames, hwf, background=None, pose_c=None, savedir=None, save_disparity=False, log=print, shard=None):
+def render_frames(model, cfg, frames, hwf, background=None, pose_c=None, savedir=None, save_disparity=False, log=print, shard=None,
+                  fused_products=False):
     """frames: iterable of dict(pose (3|4,4), audio (16,29) [AudioFaceModel] or expression (76,) [NeRFaceModel], mask (H,W,12)
     optional, name optional).
     hwf = (H, W, intrinsics[fx, fy, cx, cy]).  Returns the list of per-frame outputs (dicts of tensors).
     shard (True | process group): the node renders each frame together -- every rank (one process per GPU, torch.distributed
     initialised, the same frames on every rank) renders its block of the frame's rays and one RCCL all-gather assembles the frame on
     all of them (run_one_iter_of_nerf(_shard=...)); rank 0 writes the images.  The draws of frame i are keyed by (randomseed + i, global
-    ray index), so the images do not depend on the number of GPUs; shard=None keeps the reference's torch.rand stream."""
+    ray index), so the images do not depend on the number of GPUs; shard=None keeps the reference's torch.rand stream.
+    fused_products: one ops.frame_products call per frame forms what is written -- image, mask, normal and disparity bytes -- on the GPU
+    in place of normal_map, label2color and the casts; each output dict gains ``bytes`` (those uint8 GPU tensors), ``normals`` is the
+    op's fp32 plane, and a PNG costs one host copy of its bytes.  The render itself is not touched."""
     H, W, focal = hwf
     results, times = [], []
     dev = next(model.parameters()).device
@@ -106,16 +111,24 @@ def render_frames(model, cfg, frames, hwf, background=None, pose_c=None, savedir
                 H, W, focal, model, ro, rd, cfg, mode="validation", driving=audio, pose=pose, pose_c=pose_c, background_prior=bg,
                 latent_code=None, inHead=mask, _shard=shard if sharded else None)
             rgb = rgb_f if rgb_f is not None else rgb_c
-            normals = normal_map(disp_f, focal, w_bg, clean=True)
+            if fused_products:
+                planes = ops.frame_products(rgb, disp_f, w_bg, focal, clean=True, float_normals=True)
+                normals = planes.pop("normals_f32")
+            else:
+                normals = normal_map(disp_f, focal, w_bg, clean=True)
         torch.cuda.synchronize() if dev.type == "cuda" else None
         times.append(time.time() - t0)
         if savedir and writer:
             name = str(fr.get("name", "f_%04d.png" % i)).split("/")[-1].split(".")[0] + ".png"
-            _save_png(os.path.join(savedir, name), cast_to_image(rgb[..., :3]))
-            _save_png(os.path.join(savedir, "masks", name), cast_to_image(label2color(rgb[..., 3:])))
-            _save_png(os.path.join(savedir, "normals", name), normals.clamp(0, 255).to(torch.uint8).cpu().numpy())
-            if save_disparity:
-                _save_png(os.path.join(savedir, "disparity", name), cast_to_disparity_image(disp_f))
-        results.append(dict(rgb=rgb, disp=disp_f, depth=depth_f, w_bg=w_bg, normals=normals))
+            if fused_products:
+                for sub, key in (("", "image"), ("masks", "seg"), ("normals", "normals")) + ((("disparity", "disparity"),) if save_disparity else ()):
+                    _save_png(os.path.join(savedir, sub, name), planes[key].cpu().numpy())
+            else:
+                _save_png(os.path.join(savedir, name), cast_to_image(rgb[..., :3]))
+                _save_png(os.path.join(savedir, "masks", name), cast_to_image(label2color(rgb[..., 3:])))
+                _save_png(os.path.join(savedir, "normals", name), normals.clamp(0, 255).to(torch.uint8).cpu().numpy())
+                if save_disparity:
+                    _save_png(os.path.join(savedir, "disparity", name), cast_to_disparity_image(disp_f))
+        results.append(dict(rgb=rgb, disp=disp_f, depth=depth_f, w_bg=w_bg, normals=normals, **(dict(bytes=planes) if fused_products else {})))
         log("Avg time per image: %s" % (sum(times) / (i + 1)))
     return results

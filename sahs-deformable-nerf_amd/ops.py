@@ -509,6 +509,71 @@ def image_metrics(a, b, data_range=1.0, ssim_data_range=None, channels_last=True
     return out if batched else out[0]
 
 
+FRAME_PRODUCTS_TILE = 32      # include/sahs_nerf.h: SAHS_FRAME_PRODUCTS_TILE
+
+
+def frame_products(rgb, disp=None, w_bg=None, focal=None, clean=True, central_difference=False, float_normals=False):
+    """What Stage-I evaluation writes for a rendered frame, as bytes, in at most two launches whatever the batch (include/sahs_nerf.h:
+    sahs_frame_products; evaluation.py's cast_to_image, label2color, normal_map and cast_to_disparity_image are its statement).
+    rgb: float32 GPU tensor (H, W, C) or (B, H, W, C), C = 3 or 15 ([rgb3 | seg12], the renderer's output), read in place through
+    its batch, row and column strides (channel stride 1: a [..., :3] view of the render is read in place; anything else is copied).
+    disp, w_bg: float32 (H, W) or (B, H, W), optional.  focal: the intrinsics [fx, fy, cx, cy] (cx, cy as fractions), optional.
+    -> dict of GPU tensors, a key present exactly when its inputs were given:
+      image      uint8 (.., H, W, 3)                    always
+      seg        uint8 (.., H, W, 3)                    C = 15
+      disparity  uint8 (.., H, W)                       disp
+      normals    uint8 (.., H - d, W - d, 3)            disp and focal (w_bg and clean: whitened and blended); d = 2 with central_difference, else 1
+      normals_f32  float32, the same before the clamp   disp and focal, and float_normals (asking for it without them is refused)
+    A NaN that reaches a byte is stored as 0; a frame whose disparity holds a NaN, or is constant, gets an all-zero disparity plane.
+    Rectangular maps: the column index enters x with cx * W, the row index y with cy * H.  No gradient."""
+    for t, name in ((rgb, "rgb"), (disp, "disp"), (w_bg, "w_bg")):
+        if t is None and name != "rgb":
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.SahsError("frame_products: %s must be a GPU tensor (the HIP path has no CPU fallback)" % name)
+        if t.device.index != torch.cuda.current_device():
+            raise _lib.SahsError("frame_products: %s lives on %s but the current device is cuda:%d" % (name, t.device, torch.cuda.current_device()))
+        if t.dtype != torch.float32:
+            raise _lib.SahsError("frame_products: %s must be torch.float32, got %s" % (name, t.dtype))
+    if rgb.dim() not in (3, 4):
+        raise _lib.SahsError("frame_products: rgb must be (H, W, C) or (B, H, W, C), got %s" % (tuple(rgb.shape),))
+    batched = rgb.dim() == 4
+    rgb = rgb.detach() if batched else rgb.detach()[None]
+    B, H, W, C = rgb.shape
+    if rgb.stride(3) != 1 and C > 1:
+        rgb = rgb.contiguous()
+    planes = []
+    for t, name in ((disp, "disp"), (w_bg, "w_bg")):
+        if t is not None:
+            if tuple(t.shape) != ((B, H, W) if batched else (H, W)):
+                raise _lib.SahsError("frame_products: %s is %s, rgb is %s: needs rgb's frames and pixels" % (name, tuple(t.shape), tuple(rgb.shape)))
+            t = t.detach().contiguous()
+        planes.append(t)
+    disp, w_bg = planes
+    intr = None if focal is None else (ctypes.c_float * 4)(*[float(v) for v in focal])
+    d = 2 if central_difference else 1
+    dev = rgb.device
+    lead = (B,) if batched else ()
+    u8 = lambda *shape: torch.empty(lead + shape, dtype=torch.uint8, device=dev)      # noqa: E731
+    out = {"image": u8(H, W, 3)}
+    if C == 15:
+        out["seg"] = u8(H, W, 3)
+    if disp is not None:
+        out["disparity"] = u8(H, W)
+        if focal is not None:
+            out["normals"] = u8(max(H - d, 0), max(W - d, 0), 3)
+    if float_normals:      # asked for: without disp and focal the C side refuses, with its message
+        out["normals_f32"] = torch.empty(lead + (max(H - d, 0), max(W - d, 0), 3), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    need = int(L.sahs_frame_products_workspace_bytes(B, H, W)) if disp is not None else 0
+    work = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=dev)
+    strides = (ctypes.c_long * 3)(*rgb.stride()[:3])
+    check(L.sahs_frame_products(_p(rgb), C, strides, _p(disp), _p(w_bg), intr, B, H, W, int(bool(clean)), int(bool(central_difference)),
+                                _p(out["image"]), _p(out.get("seg")), _p(out.get("normals")), _p(out.get("normals_f32")),
+                                _p(out.get("disparity")), _p(work), need, _stream()), "sahs_frame_products")
+    return out
+
+
 LPIPS_TILE, LPIPS_MAX_JOBS, LPIPS_MAX_CHANNELS, LPIPS_MIN_SIDE = 256, 5, 1024, 31      # include/sahs_nerf.h: SAHS_LPIPS_*
 
 
