@@ -451,6 +451,34 @@ size_t sahs_image_metrics_workspace_bytes(long B, int H, int W, int C);
 int sahs_image_metrics(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
                        double ssim_data_range, double *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- image loss: clamp, MSE, L1 and windowed SSIM as one differentiable objective, fused (the reference's Stage-II step trains on
+ * the MSE of the clamped output and keeps the l2 + l1 variant one comment away: train_get_texture_photo_audio.py:189-191) ----
+ *   loss = w_l2 MSE(x, t) + w_l1 L1(x, t) + w_ssim (1 - SSIM(x, t)),   x = clamp(pred, 0, 1) when clamp != 0, else pred.
+ * pred, target: B fp32 images of H x W pixels and C channels (1 .. 4), each addressed by its own four ELEMENT strides
+ * (batch, row, column, channel) as sahs_image_metrics addresses them: host arrays read before the call returns, strides >= 0.
+ * MSE and L1 are means over H * W * C elements; SSIM is sahs_image_metrics' (7 x 7 uniform window, sample covariance, C1 = (0.01 R)^2,
+ * C2 = (0.03 R)^2 with R = ssim_data_range, the mean over the (H - 6)(W - 6) windows inside the image, then over the channels).
+ * out: 4 + 3 B doubles: [loss, MSE, L1, mean SSIM] of the batch -- the means of the rows -- then one row [MSE, L1, mean SSIM] per image.
+ * grad: null, or B fp32 images addressed by stride_grad (distinct elements: every one is written once, by one thread).  It receives
+ * the gradient with respect to pred of EACH IMAGE'S OWN loss, w_l2 MSE_b + w_l1 L1_b + w_ssim (1 - SSIM_b): the gradient of the
+ * batch's loss under an upstream gradient g is grad * (g / B), one scaling, which is the caller's.  The clamp passes the gradient
+ * where 0 <= pred <= 1, both ends included (and -0.0 with them); L1's derivative at x == t is 0.  With grad null no gradient work is
+ * done, and out has the same bits.
+ * workspace: sahs_image_loss_workspace_bytes(B, H, W, C) bytes, 8-byte aligned (one record of C + 2 doubles per image and tile of
+ * SAHS_IMAGE_LOSS_TILE^2 pixels); 0 from the query means the shape is invalid.
+ * Two launches whatever B is, no atomics, every sum in float64 and in a fixed order that does not depend on B: results are
+ * bit-reproducible, and a batch gives the bits of its single calls, rows and gradient alike.  The window moments are centred (a shift
+ * per tile and channel), and the gradient's window coefficients are formed in the shifted frame.
+ * Invalid, refused before any HIP call: a null pred, target, stride array, out or workspace, or a grad without stride_grad; B < 0
+ * (B == 0 succeeds without a launch) or B * tiles >= 2^31; H < 7 or W < 7 or > 32768; C outside 1 .. 4; a negative stride; a weight
+ * that is not finite; ssim_data_range not finite or <= 0; pred, target or grad not aligned to its 4-byte element, out or workspace
+ * not to 8 bytes; workspace_bytes below the query's value. */
+#define SAHS_IMAGE_LOSS_TILE 32
+size_t sahs_image_loss_workspace_bytes(long B, int H, int W, int C);
+int sahs_image_loss(const float *pred, const float *target, long B, int H, int W, int C, const long *stride_pred, const long *stride_target,
+                    double w_l2, double w_l1, double w_ssim, int clamp, double ssim_data_range, float *grad, const long *stride_grad,
+                    double *out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- LPIPS (net = alex, v0.1): the scaling layer and the distance head, fused (the reference scores frames with the lpips package:
  * nerf/metrics.py).  The five AlexNet feature maps between the two calls are the caller's convolutions (metrics.py: LPIPS).
  * sahs_lpips_prepare -- a, b: B images of H x W pixels and 3 channels, both SAHS_IMAGE_U8 (taken as x / 255) or both SAHS_IMAGE_F32,

@@ -85,6 +85,9 @@ SIGNATURES = {
     "sahs_spectral_norm_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "sahs_image_metrics_workspace_bytes": (ctypes.c_size_t, [_L, _I, _I, _I]),
     "sahs_image_metrics": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
+    "sahs_image_loss_workspace_bytes": (ctypes.c_size_t, [_L, _I, _I, _I]),
+    "sahs_image_loss": (_I, [_P, _P, _L, _I, _I, _I, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, ctypes.c_double, _P, _P, _P, _P,
+                        ctypes.c_size_t, _P]),
     "sahs_lpips_prepare": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _I, _P, _P]),
     "sahs_lpips_distance_workspace_bytes": (ctypes.c_size_t, [_I, _L, _P]),
     "sahs_lpips_distance": (_I, [_I, _P, _P, _P, _P, _L, _P, _P, ctypes.c_size_t, _P]),

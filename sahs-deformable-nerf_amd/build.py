@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsahs_nerf.so")
-SOURCES = ["capi.hip", "pack.hip", "render_ops.hip", "spade_ops.hip", "spectral_norm.hip", "image_metrics.hip", "lpips.hip", "frame_products.hip", "optim.hip", "field_f32.hip", "field_bf16w.hip", "field_bf16x3.hip", "field_bwd.hip", "field_bwd_tn_jobs.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip", "train_bwd.hip"]
+SOURCES = ["capi.hip", "pack.hip", "render_ops.hip", "spade_ops.hip", "spectral_norm.hip", "image_metrics.hip", "image_loss.hip", "lpips.hip", "frame_products.hip", "optim.hip", "field_f32.hip", "field_bf16w.hip", "field_bf16x3.hip", "field_bwd.hip", "field_bwd_tn_jobs.hip", "field_bwd_chain.hip", "field_bwd_chain_f32.hip", "train_bwd.hip"]
 # sources built again for the NeRFaceModel architectures (csrc/sahs_model.hpp: -DSAHS_MODEL=1 / 2, symbols suffixed _nf / _ns);
 # field_bwd_tn_jobs.hip and field_bwd_gemm.hip, which it includes (ONE translation unit: apart, every kernel of both gets another prologue),
 # read no layout constant and are built once (every model's field_bwd.hip calls their launchers)
@@ -38,6 +38,7 @@ NO_SCRATCH = {"gemm_dma_kernel": 0, "_ZN4sahs24field_forward_f32_kernelILb0E": 0
               "spectral_norm_vectors_kernel": 0, "spectral_norm_scale_kernel": 0, "spectral_norm_backward_kernel": 0,      # (1024-thread workgroups: 128 registers)
               "field_backward_chain_rad_f32_kernel": 0, "field_backward_chain_def_f32_kernel": 0,
               "image_metrics_tile_kernel": 0,      # (its channel loop must stay a loop: unrolled, four channels' float64 accumulators spill)
+              "image_loss_tile_kernel": 0, "image_loss_finalize_kernel": 0,      # (the same channel loop, 35 float64 accumulators per thread)
               "lpips_prepare_kernel": 0, "lpips_distance_tile_kernel": 0, "lpips_distance_finalize_kernel": 0,      # (streaming; five float64 sums per thread)
               "frame_products_tile_kernel": 0, "frame_products_disparity_kernel": 0,      # (a pixel per thread: its 15 values stay in LDS, not in an indexed array)
               # (the names above match by substring, whichever file or namespace a kernel lives in -- the gemm_* ones are in field_bwd_gemm.hip

@@ -409,6 +409,53 @@ int sahs_image_metrics(const void *a, const void *b, int dtype, long B, int H, i
     return e ? hip_fail(who, e) : 0;
 }
 
+// image loss: every refusal names what it refuses, before any HIP call
+static bool image_loss_shape(long B, int H, int W, int C)
+{
+    return B >= 0 && H >= 7 && W >= 7 && H <= 32768 && W <= 32768 && C >= 1 && C <= 4 && B * sahs_image_loss_tiles(H, W) < 2147483648L;
+}
+
+size_t sahs_image_loss_workspace_bytes(long B, int H, int W, int C)
+{
+    return image_loss_shape(B, H, W, C) ? (size_t)B * (size_t)sahs_image_loss_tiles(H, W) * (size_t)(C + 2) * sizeof(double) : 0;
+}
+
+int sahs_image_loss(const float *pred, const float *target, long B, int H, int W, int C, const long *stride_pred, const long *stride_target,
+                    double w_l2, double w_l1, double w_ssim, int clamp, double ssim_data_range, float *grad, const long *stride_grad,
+                    double *out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "sahs_image_loss";
+    if (H < 7 || W < 7 || H > 32768 || W > 32768)
+        return fail(1, "%s: images of %d x %d pixels, the 7 x 7 window needs 7 <= H, W (<= 32768) (capi.hip:%d)", who, H, W, __LINE__);
+    if (C < 1 || C > 4) return fail(1, "%s: C = %d channels, must be 1 .. 4 (capi.hip:%d)", who, C, __LINE__);
+    if (!image_loss_shape(B, H, W, C))
+        return fail(1, "%s: B = %ld images, needs B >= 0 and B * tiles < 2^31 (capi.hip:%d)", who, B, __LINE__);
+    if (!std::isfinite(w_l2) || !std::isfinite(w_l1) || !std::isfinite(w_ssim))
+        return fail(1, "%s: weights w_l2 = %g, w_l1 = %g, w_ssim = %g, must be finite (capi.hip:%d)", who, w_l2, w_l1, w_ssim, __LINE__);
+    if (!(ssim_data_range > 0.0) || !std::isfinite(ssim_data_range))
+        return fail(1, "%s: ssim_data_range = %g, must be finite and > 0 (capi.hip:%d)", who, ssim_data_range, __LINE__);
+    if (B == 0) return 0;
+    if (!pred || !target || !stride_pred || !stride_target || !out || !workspace || (grad && !stride_grad))
+        return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !pred ? "pred" : !target ? "target" : !stride_pred ? "stride_pred" :
+                    !stride_target ? "stride_target" : !out ? "out" : !workspace ? "workspace" : "stride_grad (grad asked for)", __LINE__);
+    for (int k = 0; k < 4; ++k)
+        if (stride_pred[k] < 0 || stride_target[k] < 0 || (grad && stride_grad[k] < 0))
+            return fail(1, "%s: stride %d is negative (%ld, %ld, grad %ld) (capi.hip:%d)", who, k, stride_pred[k], stride_target[k],
+                        grad ? stride_grad[k] : 0L, __LINE__);
+    if (((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target)) & 3u) != 0)
+        return fail(1, "%s: pred and target must be aligned to their 4-byte elements (capi.hip:%d)", who, __LINE__);
+    if ((reinterpret_cast<uintptr_t>(grad) & 3u) != 0)
+        return fail(1, "%s: grad must be aligned to its 4-byte elements (capi.hip:%d)", who, __LINE__);
+    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7u) != 0)
+        return fail(1, "%s: out and workspace must be 8-byte aligned (capi.hip:%d)", who, __LINE__);
+    const size_t need = sahs_image_loss_workspace_bytes(B, H, W, C);
+    if (workspace_bytes < need)
+        return fail(1, "%s: workspace of %zu bytes, needs %zu (sahs_image_loss_workspace_bytes) (capi.hip:%d)", who, workspace_bytes, need, __LINE__);
+    int e = sahs_image_loss_launch(pred, target, B, H, W, C, stride_pred, stride_target, w_l2, w_l1, w_ssim, clamp, ssim_data_range, grad,
+                                   stride_grad, out, static_cast<double *>(workspace), (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
 // frame products: every refusal names what it refuses, before any HIP call
 static bool frame_products_shape(long B, int H, int W)
 {

@@ -71,6 +71,11 @@ int sahs_spectral_norm_backward_launch(int jobs, const float *const *W, const fl
 long sahs_image_metrics_tiles(int H, int W);
 int sahs_image_metrics_launch(const void *a, const void *b, int is_float, long B, int H, int W, int C, const long *stride_a,
                               const long *stride_b, double ssim_data_range, double *out, double *records, hipStream_t stream);
+// image_loss.hip (arguments already validated: capi.hip; records: sahs_image_loss_tiles(H, W) * B * (C + 2) doubles; grad may be null)
+long sahs_image_loss_tiles(int H, int W);
+int sahs_image_loss_launch(const float *pred, const float *target, long B, int H, int W, int C, const long *stride_pred,
+                           const long *stride_target, double w_l2, double w_l1, double w_ssim, int clamp, double ssim_data_range,
+                           float *grad, const long *stride_grad, double *out, double *records, hipStream_t stream);
 // lpips.hip (arguments already validated: capi.hip; records: B * sahs_lpips_distance_tiles(jobs, hw) doubles)
 int sahs_lpips_prepare_launch(const void *a, const void *b, int is_float, long B, int H, int W, const long *stride_a, const long *stride_b,
                               int normalize, float *out, hipStream_t stream);

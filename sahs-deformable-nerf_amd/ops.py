@@ -509,6 +509,85 @@ def image_metrics(a, b, data_range=1.0, ssim_data_range=None, channels_last=True
     return out if batched else out[0]
 
 
+IMAGE_LOSS_TILE = 32      # include/sahs_nerf.h: SAHS_IMAGE_LOSS_TILE
+
+
+def _image_loss_forward(pred, target, weights, clamp, ssim_data_range, grad):
+    """pred, target, grad (or None): (B, H, W, C) views -> the float64 ``out`` of sahs_image_loss, 4 + 3 B values."""
+    B, H, W, C = pred.shape
+    L = _lib.lib()
+    out = torch.empty(4 + 3 * B, dtype=torch.float64, device=pred.device)
+    need = int(L.sahs_image_loss_workspace_bytes(B, H, W, C))
+    work = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=pred.device)
+    strides = [None if t is None else (ctypes.c_long * 4)(*t.stride()) for t in (pred, target, grad)]
+    check(L.sahs_image_loss(_p(pred), _p(target), B, H, W, C, strides[0], strides[1], weights[0], weights[1], weights[2], int(bool(clamp)),
+                            float(ssim_data_range), _p(grad), strides[2], _p(out), _p(work), need, _stream()), "sahs_image_loss")
+    return out
+
+
+class ImageLossFn(torch.autograd.Function):
+    """image_loss as ONE differentiable node: the forward's two launches also write the gradient image of each image's own loss, and the
+    backward is one scaling of it by grad_out / B.  pred, target: (B, H, W, C) views.  -> (loss, rows); rows carries no gradient.
+    Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weights, clamp, ssim_data_range):
+        grad = torch.empty_like(pred)      # (pred's strides where they are dense, so the permuted view of an NCHW tensor is written NCHW)
+        out = _image_loss_forward(pred.detach(), target, weights, clamp, ssim_data_range, grad)
+        _save_named(ctx, grad=grad)
+        ctx.batch = pred.shape[0]
+        rows = out[4:].view(-1, 3)
+        ctx.mark_non_differentiable(rows)
+        return out[0].float(), rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_rows):
+        return _load_named(ctx).grad * (grad_loss * (1.0 / ctx.batch)), None, None, None, None
+
+
+def image_loss(pred, target, l2=1.0, l1=0.0, ssim=0.0, clamp=True, ssim_data_range=1.0, channels_last=False, return_terms=False):
+    """The refiner's objective, fused and differentiable (include/sahs_nerf.h: sahs_image_loss; two launches whatever the batch):
+        loss = l2 * MSE(x, t) + l1 * L1(x, t) + ssim * (1 - SSIM(x, t)),   x = pred.clamp(0, 1) if clamp else pred,
+    MSE and L1 the means over all elements, SSIM image_metrics' (7x7 uniform window, sample covariance, at ``ssim_data_range``), averaged
+    over the batch.  pred, target: float32 GPU tensors of ONE shape, (C, H, W) or (B, C, H, W) -- with channels_last=True (H, W, C) or
+    (B, H, W, C) -- C = 1 .. 4, H, W >= 7, read in place through their strides.
+    -> the loss, a 0-d float32 tensor; with return_terms=True (loss, rows), rows the detached float64 (B, 3) [MSE, L1, mean SSIM] of
+    each image.  The gradient flows to ``pred`` only (ImageLossFn: the forward forms it, the backward scales it; it has pred's shape),
+    through the clamp where 0 <= pred <= 1; ``target`` must not require one.  When pred asks for no gradient, or under no_grad, the
+    kernel skips the gradient's work and returns the same bits.  Bit-reproducible; a batch gives the bits of its single calls.
+    Runs outside autocast."""
+    for t, name in ((pred, "pred"), (target, "target")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.SahsError("image_loss: %s must be a GPU tensor (the HIP path has no CPU fallback)" % name)
+        if t.device.index != torch.cuda.current_device():
+            raise _lib.SahsError("image_loss: %s lives on %s but the current device is cuda:%d" % (name, t.device, torch.cuda.current_device()))
+        if t.dtype != torch.float32:
+            raise _lib.SahsError("image_loss: %s must be torch.float32, got %s (under autocast: pred.float())" % (name, t.dtype))
+    if target.requires_grad:
+        raise _lib.SahsError("image_loss: target requires a gradient, and the gradient is formed for pred only (pass target.detach())")
+    if pred.shape != target.shape or pred.dim() not in (3, 4):
+        raise _lib.SahsError("image_loss: pred and target must have one shape, (C, H, W) or (B, C, H, W) (channels_last=True: (H, W, C) or "
+                             "(B, H, W, C)), got %s and %s" % (tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() == 3:
+        pred, target = pred[None], target[None]
+    if not channels_last:
+        pred, target = pred.permute(0, 2, 3, 1), target.permute(0, 2, 3, 1)      # views: the kernel reads through the strides
+    B, H, W, C = pred.shape
+    if H < 7 or W < 7:
+        raise _lib.SahsError("image_loss: pred is %d x %d pixels, the 7 x 7 SSIM window needs H, W >= 7" % (H, W))
+    if not 1 <= C <= 4:
+        raise _lib.SahsError("image_loss: pred has C = %d channels, must be 1 .. 4 (channels_last=%r)" % (C, bool(channels_last)))
+    weights = (float(l2), float(l1), float(ssim))
+    with torch.autocast("cuda", enabled=False):
+        if torch.is_grad_enabled() and pred.requires_grad:
+            loss, rows = ImageLossFn.apply(pred, target, weights, bool(clamp), float(ssim_data_range))
+        else:
+            out = _image_loss_forward(pred.detach(), target, weights, clamp, ssim_data_range, None)
+            loss, rows = out[0].float(), out[4:].view(-1, 3)
+    return (loss, rows) if return_terms else loss
+
+
 FRAME_PRODUCTS_TILE = 32      # include/sahs_nerf.h: SAHS_FRAME_PRODUCTS_TILE
 
 

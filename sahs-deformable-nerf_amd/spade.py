@@ -288,21 +288,43 @@ def refine_learning_rate(cfg, epoch):
     return t.lr_G / t.epochs_decay * (t.epochs + t.epochs_decay - epoch)
 
 
-def refine_step(G, optimizer, I_src, I_raw, target, driving=None, autocast_dtype=None):
+class RefineLoss:
+    """A training objective for ``refine_step``: ``l2 * MSE + l1 * L1 + ssim * (1 - SSIM)`` between the clamped output and the target --
+    what a refiner is scored on (metrics.score_frames: L1, PSNR, SSIM) -- as ONE fused, differentiable op with the clamp inside
+    (ops.image_loss: two launches forward, one scaling backward, bit-reproducible).  ``RefineLoss()`` is the reference's objective,
+    ``RefineLoss(1, 1)`` the l2 + l1 variant its audio loop keeps commented (train_get_texture_photo_audio.py:189-191).  Under
+    autocast the generator's bf16 output is widened first; the op itself runs in fp32 outside autocast."""
+
+    def __init__(self, l2=1.0, l1=0.0, ssim=0.0, ssim_data_range=1.0):
+        self.l2, self.l1, self.ssim, self.ssim_data_range = float(l2), float(l1), float(ssim), float(ssim_data_range)
+
+    def __call__(self, fake, target):
+        return ops.image_loss(fake.float(), target, l2=self.l2, l1=self.l1, ssim=self.ssim, clamp=True, ssim_data_range=self.ssim_data_range)
+
+    def __repr__(self):
+        return "RefineLoss(l2=%g, l1=%g, ssim=%g, ssim_data_range=%g)" % (self.l2, self.l1, self.ssim, self.ssim_data_range)
+
+
+def refine_step(G, optimizer, I_src, I_raw, target, driving=None, loss=None, autocast_dtype=None):
     """One training step of the Stage-II generator, train_get_texture_photo.py:168-179 (``driving`` = the audio window of
     train_get_texture_photo_audio.py:143-192 for Generator_audio): MSE between the clamped output and the target frame, backward,
     optimiser step.  Returns the loss (a 0-d tensor; no synchronisation here).  The caller does ``G.train()``, the data loading and the
     learning-rate schedule, as with training.train_step.
+    loss=None is the reference's objective in torch's own ops; a ``RefineLoss`` takes the place of the clamp and the MSE with its
+    weighted MSE / L1 / SSIM objective, and nothing else in the step changes (any callable ``(fake, target) -> 0-d loss`` is taken).
     autocast_dtype=torch.bfloat16 (not in the reference): the generator's forward and the loss run under
     ``torch.autocast("cuda", dtype=torch.bfloat16)`` -- the convolutions on the bf16 matrix pipe, the SPADE modulation on its bf16
     kernels -- while backward() and the optimiser step run outside it; the parameters and Adam's state stay fp32, and bf16 has fp32's
     exponent range, so there is no GradScaler."""
     if autocast_dtype not in (None, torch.bfloat16):
         raise ValueError("refine_step: autocast_dtype must be None or torch.bfloat16, got %r" % (autocast_dtype,))
+    if loss is not None and not callable(loss):
+        raise ValueError("refine_step: loss must be None or a callable (fake, target) -> loss such as RefineLoss, got %r "
+                         "(autocast_dtype is passed by keyword)" % (loss,))
     optimizer.zero_grad()
     with contextlib.nullcontext() if autocast_dtype is None else torch.autocast("cuda", dtype=autocast_dtype):
         fake = G(I_src, I_raw) if driving is None else G(I_src, I_raw, driving)
-        loss = F.mse_loss(fake.clamp(0, 1), target)
+        loss = F.mse_loss(fake.clamp(0, 1), target) if loss is None else loss(fake, target)
     loss.backward()
     optimizer.step()
     return loss.detach()
