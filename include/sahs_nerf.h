@@ -514,6 +514,42 @@ size_t sahs_lpips_distance_workspace_bytes(int jobs, long B, const long *hw);
 int sahs_lpips_distance(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
                         double *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- LPIPS as a training term: the same two ends, differentiable with respect to the FIRST operand (pred) only; the convolutions
+ * between them, and their backward, stay the caller's.  Not twice differentiable.
+ * sahs_lpips_prepare_loss -- sahs_lpips_prepare with pred fp32, target SAHS_IMAGE_U8 or SAHS_IMAGE_F32 (target_dtype), and a clamp
+ * flag: clamp != 0 applies min(max(x, 0), 1) to pred alone, ahead of the optional 2x - 1 and the scaling layer (a NaN stays a NaN).
+ * out: the one (2B, 3, H, W) tensor, rows [0, B) from pred.  One launch; sahs_lpips_prepare is this kernel with the flag off.
+ * sahs_lpips_prepare_grad -- its backward, one launch, a thread per pixel.  gx: the contiguous (B, 3, H, W) fp32 gradient of rows
+ * [0, B) of out.  grad, B images addressed by stride_grad (distinct elements, each written once), receives
+ *   grad[c] = gx[c] / scale_c   (one correctly rounded fp32 division; times 2, exact, when normalize != 0),
+ * and +0 where clamp != 0 and pred is not in [0, 1] (both ends pass; a NaN pred passes nothing), as torch.clamp's backward gives.
+ * sahs_lpips_head_forward -- sahs_lpips_distance with each layer's two operands as two contiguous (B, C[l], h, w) tensors fa[l], fb[l];
+ * out and workspace as there (sahs_lpips_distance_workspace_bytes), and the same bits: sahs_lpips_distance is this entry with
+ * fb[l] = features[l] + B C[l] hw[l].  stats: null, or sahs_lpips_head_stats_bytes(jobs, B, hw) bytes, 8-byte aligned, which receive
+ * what the backward needs of each pixel's five sums -- with sa = sum a^2, swa = sum w a^2, swab = sum w a b:
+ *   ra = 1 / na,   rb = 1 / nb,   q = (swa / na - swab / nb) / (sqrt(sa) na),   q = 0 where sa == 0
+ * -- as three planes of B * sum_l hw[l] doubles (24 bytes per pixel beside its 8 C[l] bytes of features).  It is a buffer of its own,
+ * not part of the workspace, because it must live until the backward and the workspace need not.  out has the same bits either way.
+ * sahs_lpips_head_backward -- one launch over all layers (the forward's job table and tile mapping, a thread per pixel walking the
+ * channels; fa, fb, weights, C, hw, B and stats as the forward had them).  g: the upstream gradient of each image's LPIPS, B doubles
+ * (g_is_double != 0) or B floats, widened.  grad_a[l], fa[l]'s shape, every element written once, no atomics:
+ *   grad_a[c] = (float)( (2 g_i / hw) ra ( w_c (a_c ra - b_c rb) - a_c q ) ),   float64 arithmetic, rounded to fp32 once;
+ * this is d/da_c of g_i * mean over pixels of sum_c w_c (a_c / na - b_c / nb)^2.  At a pixel whose a is all zero a -> a / (|a| + 1e-10)
+ * has the Jacobian I / 1e-10, so q = 0 there is the derivative itself: the result is large (2 w_c b_c rb 1e10 g_i / hw) and finite, where
+ * autograd of the published formula gives NaN (sqrt's derivative at 0).  Equal operands give a gradient that is exactly 0.
+ * Invalid, refused with a message that names it before any HIP call: as sahs_lpips_prepare and sahs_lpips_distance refuse, for the
+ * tables fa and fb alike; a null gx, grad, stride_grad, g, stats (backward) or grad_a[l]; a negative stride; a misaligned pointer
+ * (g to its 4- or 8-byte element); stats_bytes below the query's value. */
+int sahs_lpips_prepare_loss(const float *pred, const void *target, int target_dtype, long B, int H, int W, int C, const long *stride_pred,
+                            const long *stride_target, int normalize, int clamp, float *out, void *stream);
+int sahs_lpips_prepare_grad(const float *pred, const float *gx, long B, int H, int W, int C, const long *stride_pred, int normalize, int clamp,
+                            float *grad, const long *stride_grad, void *stream);
+size_t sahs_lpips_head_stats_bytes(int jobs, long B, const long *hw);
+int sahs_lpips_head_forward(int jobs, const float *const *fa, const float *const *fb, const float *const *weights, const int *C, const long *hw,
+                            long B, double *out, double *stats, size_t stats_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int sahs_lpips_head_backward(int jobs, const float *const *fa, const float *const *fb, const float *const *weights, const int *C, const long *hw,
+                             long B, const void *g, int g_is_double, const double *stats, size_t stats_bytes, float *const *grad_a, void *stream);
+
 /* ---- frame products: the bytes Stage-I evaluation writes for a rendered frame, fused (the reference's eval_stage_rays.py tail: image
  * and disparity casts, torch_normal_map, nerf/utils.py label2color) ----
  * For B frames of H x W pixels.  Inputs (device pointers):

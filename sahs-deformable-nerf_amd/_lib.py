@@ -91,6 +91,11 @@ SIGNATURES = {
     "sahs_lpips_prepare": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _I, _P, _P]),
     "sahs_lpips_distance_workspace_bytes": (ctypes.c_size_t, [_I, _L, _P]),
     "sahs_lpips_distance": (_I, [_I, _P, _P, _P, _P, _L, _P, _P, ctypes.c_size_t, _P]),
+    "sahs_lpips_prepare_loss": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    "sahs_lpips_prepare_grad": (_I, [_P, _P, _L, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "sahs_lpips_head_stats_bytes": (ctypes.c_size_t, [_I, _L, _P]),
+    "sahs_lpips_head_forward": (_I, [_I, _P, _P, _P, _P, _P, _L, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
+    "sahs_lpips_head_backward": (_I, [_I, _P, _P, _P, _P, _P, _L, _P, _I, _P, ctypes.c_size_t, _P, _P]),
     "sahs_frame_products_workspace_bytes": (ctypes.c_size_t, [_L, _I, _I]),
     "sahs_frame_products": (_I, [_P, _I, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "sahs_probe_arm": (_I, [_I]),

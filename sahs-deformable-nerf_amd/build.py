@@ -40,6 +40,7 @@ NO_SCRATCH = {"gemm_dma_kernel": 0, "_ZN4sahs24field_forward_f32_kernelILb0E": 0
               "image_metrics_tile_kernel": 0,      # (its channel loop must stay a loop: unrolled, four channels' float64 accumulators spill)
               "image_loss_tile_kernel": 0, "image_loss_finalize_kernel": 0,      # (the same channel loop, 35 float64 accumulators per thread)
               "lpips_prepare_kernel": 0, "lpips_distance_tile_kernel": 0, "lpips_distance_finalize_kernel": 0,      # (streaming; five float64 sums per thread)
+              "lpips_prepare_grad_kernel": 0, "lpips_head_backward_kernel": 0,      # (streaming; the channel loop stays a loop)
               "frame_products_tile_kernel": 0, "frame_products_disparity_kernel": 0,      # (a pixel per thread: its 15 values stay in LDS, not in an indexed array)
               # (the names above match by substring, whichever file or namespace a kernel lives in -- the gemm_* ones are in field_bwd_gemm.hip
               # and field_bwd_tn_jobs.hip, built once -- and so every model's build; the NeRFaceModel instances of the fused walk's chains, spelled out)

@@ -513,13 +513,11 @@ int sahs_frame_products(const float *rgb, int C, const long *stride_rgb, const f
     return e ? hip_fail(who, e) : 0;
 }
 
-// LPIPS, the scaling layer and the distance head: every refusal names what it refuses, before any HIP call
-int sahs_lpips_prepare(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
-                       int normalize, float *out, void *stream)
+// LPIPS, the scaling layer and the distance head, and their backward: every refusal names what it refuses, before any HIP call
+static int lpips_prepare_checked(const char *who, const char *na, const char *nb, const void *a, const void *b, int a_is_float, int b_is_float,
+                                 long B, int H, int W, int C, const long *stride_a, const long *stride_b, int normalize, int clamp, float *out,
+                                 void *stream)
 {
-    const char *who = "sahs_lpips_prepare";
-    if (dtype != SAHS_IMAGE_U8 && dtype != SAHS_IMAGE_F32)
-        return fail(1, "%s: dtype = %d, must be SAHS_IMAGE_U8 (0) or SAHS_IMAGE_F32 (1) (capi.hip:%d)", who, dtype, __LINE__);
     if (C != 3) return fail(1, "%s: C = %d channels, LPIPS scores RGB images: C must be 3 (capi.hip:%d)", who, C, __LINE__);
     if (H < SAHS_LPIPS_MIN_SIDE || W < SAHS_LPIPS_MIN_SIDE || H > 32768 || W > 32768)
         return fail(1, "%s: images of %d x %d pixels, AlexNet's second max-pool needs %d <= H, W (<= 32768) (capi.hip:%d)", who, H, W,
@@ -528,15 +526,58 @@ int sahs_lpips_prepare(const void *a, const void *b, int dtype, long B, int H, i
         return fail(1, "%s: B = %ld images, needs B >= 0 and 2 B H W < 2^39 (capi.hip:%d)", who, B, __LINE__);
     if (B == 0) return 0;
     if (!a || !b || !stride_a || !stride_b || !out)
-        return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !a ? "a" : !b ? "b" : !stride_a ? "stride_a" : !stride_b ? "stride_b" : "out",
-                    __LINE__);
+        return fail(1, "%s: null pointer for %s%s (capi.hip:%d)", who, a && b && (!stride_a || !stride_b) ? "stride_" : "",
+                    !a ? na : !b ? nb : !stride_a ? na : !stride_b ? nb : "out", __LINE__);
     for (int k = 0; k < 4; ++k)
         if (stride_a[k] < 0 || stride_b[k] < 0)
             return fail(1, "%s: stride %d is negative (%ld, %ld) (capi.hip:%d)", who, k, stride_a[k], stride_b[k], __LINE__);
-    const uintptr_t elem = dtype == SAHS_IMAGE_F32 ? 3u : 0u;
-    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & elem) != 0 || (reinterpret_cast<uintptr_t>(out) & 3u) != 0)
-        return fail(1, "%s: a, b and out must be aligned to their 4-byte elements (capi.hip:%d)", who, __LINE__);
-    int e = sahs_lpips_prepare_launch(a, b, dtype == SAHS_IMAGE_F32, B, H, W, stride_a, stride_b, normalize != 0, out, (hipStream_t)stream);
+    if ((reinterpret_cast<uintptr_t>(a) & (a_is_float ? 3u : 0u)) != 0 || (reinterpret_cast<uintptr_t>(b) & (b_is_float ? 3u : 0u)) != 0 ||
+        (reinterpret_cast<uintptr_t>(out) & 3u) != 0)
+        return fail(1, "%s: %s, %s and out must be aligned to their 4-byte elements (capi.hip:%d)", who, na, nb, __LINE__);
+    int e = sahs_lpips_prepare_launch(a, b, a_is_float, b_is_float, B, H, W, stride_a, stride_b, normalize != 0, clamp != 0, out, (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
+int sahs_lpips_prepare(const void *a, const void *b, int dtype, long B, int H, int W, int C, const long *stride_a, const long *stride_b,
+                       int normalize, float *out, void *stream)
+{
+    const char *who = "sahs_lpips_prepare";
+    if (dtype != SAHS_IMAGE_U8 && dtype != SAHS_IMAGE_F32)
+        return fail(1, "%s: dtype = %d, must be SAHS_IMAGE_U8 (0) or SAHS_IMAGE_F32 (1) (capi.hip:%d)", who, dtype, __LINE__);
+    const int f = dtype == SAHS_IMAGE_F32;
+    return lpips_prepare_checked(who, "a", "b", a, b, f, f, B, H, W, C, stride_a, stride_b, normalize, 0, out, stream);
+}
+
+int sahs_lpips_prepare_loss(const float *pred, const void *target, int target_dtype, long B, int H, int W, int C, const long *stride_pred,
+                            const long *stride_target, int normalize, int clamp, float *out, void *stream)
+{
+    const char *who = "sahs_lpips_prepare_loss";
+    if (target_dtype != SAHS_IMAGE_U8 && target_dtype != SAHS_IMAGE_F32)
+        return fail(1, "%s: target_dtype = %d, must be SAHS_IMAGE_U8 (0) or SAHS_IMAGE_F32 (1) (capi.hip:%d)", who, target_dtype, __LINE__);
+    return lpips_prepare_checked(who, "pred", "target", pred, target, 1, target_dtype == SAHS_IMAGE_F32, B, H, W, C, stride_pred, stride_target,
+                                 normalize, clamp, out, stream);
+}
+
+int sahs_lpips_prepare_grad(const float *pred, const float *gx, long B, int H, int W, int C, const long *stride_pred, int normalize, int clamp,
+                            float *grad, const long *stride_grad, void *stream)
+{
+    const char *who = "sahs_lpips_prepare_grad";
+    if (C != 3) return fail(1, "%s: C = %d channels, LPIPS scores RGB images: C must be 3 (capi.hip:%d)", who, C, __LINE__);
+    if (H < SAHS_LPIPS_MIN_SIDE || W < SAHS_LPIPS_MIN_SIDE || H > 32768 || W > 32768)
+        return fail(1, "%s: images of %d x %d pixels, AlexNet's second max-pool needs %d <= H, W (<= 32768) (capi.hip:%d)", who, H, W,
+                    SAHS_LPIPS_MIN_SIDE, __LINE__);
+    if (B < 0 || 2 * B * (long)H * W >= 2147483648L * 256)
+        return fail(1, "%s: B = %ld images, needs B >= 0 and 2 B H W < 2^39 (capi.hip:%d)", who, B, __LINE__);
+    if (B == 0) return 0;
+    if (!pred || !gx || !stride_pred || !grad || !stride_grad)
+        return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !pred ? "pred" : !gx ? "gx" : !stride_pred ? "stride_pred" : !grad ? "grad" :
+                    "stride_grad", __LINE__);
+    for (int k = 0; k < 4; ++k)
+        if (stride_pred[k] < 0 || stride_grad[k] < 0)
+            return fail(1, "%s: stride %d is negative (%ld, grad %ld) (capi.hip:%d)", who, k, stride_pred[k], stride_grad[k], __LINE__);
+    if (((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(gx) | reinterpret_cast<uintptr_t>(grad)) & 3u) != 0)
+        return fail(1, "%s: pred, gx and grad must be aligned to their 4-byte elements (capi.hip:%d)", who, __LINE__);
+    int e = sahs_lpips_prepare_grad_launch(pred, gx, B, H, W, stride_pred, normalize != 0, clamp != 0, grad, stride_grad, (hipStream_t)stream);
     return e ? hip_fail(who, e) : 0;
 }
 
@@ -553,10 +594,16 @@ size_t sahs_lpips_distance_workspace_bytes(int jobs, long B, const long *hw)
     return lpips_distance_shape(jobs, B, hw) ? (size_t)B * (size_t)sahs_lpips_distance_tiles(jobs, hw) * sizeof(double) : 0;
 }
 
-int sahs_lpips_distance(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
-                        double *out, void *workspace, size_t workspace_bytes, void *stream)
+size_t sahs_lpips_head_stats_bytes(int jobs, long B, const long *hw)
 {
-    const char *who = "sahs_lpips_distance";
+    return lpips_distance_shape(jobs, B, hw) ? (size_t)B * (size_t)sahs_lpips_head_pixels(jobs, hw) * 3u * sizeof(double) : 0;
+}
+
+// the job table of the head's entries: 0, or the refusal's code.  ta, tb: the names of the two feature tables (tb null: one table)
+static int lpips_head_tables(const char *who, int jobs, const float *const *fa, const char *ta, const float *const *fb, const char *tb,
+                             const float *const *weights, const int *C, const long *hw, long B, bool *empty)
+{
+    *empty = false;
     if (jobs < 1 || jobs > SAHS_LPIPS_MAX_JOBS)
         return fail(1, "%s: jobs = %d, must be 1 .. %d (capi.hip:%d)", who, jobs, SAHS_LPIPS_MAX_JOBS, __LINE__);
     if (!C || !hw) return fail(1, "%s: null pointer for the table %s (capi.hip:%d)", who, !C ? "C" : "hw", __LINE__);
@@ -568,23 +615,80 @@ int sahs_lpips_distance(int jobs, const float *const *features, const float *con
     }
     if (!lpips_distance_shape(jobs, B, hw))
         return fail(1, "%s: B = %ld images, needs B >= 0 and B * tiles < 2^31 (capi.hip:%d)", who, B, __LINE__);
-    if (B == 0) return 0;
-    if (!features || !weights || !out || !workspace)
-        return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !features ? "features" : !weights ? "weights" : !out ? "out" : "workspace",
-                    __LINE__);
+    if (B == 0) { *empty = true; return 0; }
+    if (!fa || (tb && !fb) || !weights)
+        return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !fa ? ta : (tb && !fb) ? tb : "weights", __LINE__);
     for (int k = 0; k < jobs; ++k) {
-        if (!features[k] || !weights[k])
-            return fail(1, "%s: null pointer %s[%d] (capi.hip:%d)", who, !features[k] ? "features" : "weights", k, __LINE__);
-        if (((reinterpret_cast<uintptr_t>(features[k]) | reinterpret_cast<uintptr_t>(weights[k])) & 3u) != 0)
-            return fail(1, "%s: features[%d] and weights[%d] must be aligned to their 4-byte elements (capi.hip:%d)", who, k, k, __LINE__);
+        if (!fa[k] || (tb && !fb[k]) || !weights[k])
+            return fail(1, "%s: null pointer %s[%d] (capi.hip:%d)", who, !fa[k] ? ta : (tb && !fb[k]) ? tb : "weights", k, __LINE__);
+        if (((reinterpret_cast<uintptr_t>(fa[k]) | (tb ? reinterpret_cast<uintptr_t>(fb[k]) : 0u) | reinterpret_cast<uintptr_t>(weights[k])) & 3u) != 0)
+            return tb ? fail(1, "%s: %s[%d], %s[%d] and weights[%d] must be aligned to their 4-byte elements (capi.hip:%d)", who, ta, k, tb, k, k,
+                             __LINE__)
+                      : fail(1, "%s: %s[%d] and weights[%d] must be aligned to their 4-byte elements (capi.hip:%d)", who, ta, k, k, __LINE__);
     }
+    return 0;
+}
+
+int sahs_lpips_distance(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
+                        double *out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "sahs_lpips_distance";
+    bool empty;
+    if (int code = lpips_head_tables(who, jobs, features, "features", nullptr, nullptr, weights, C, hw, B, &empty)) return code;
+    if (empty) return 0;
+    if (!out || !workspace) return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !out ? "out" : "workspace", __LINE__);
     if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7u) != 0)
         return fail(1, "%s: out and workspace must be 8-byte aligned (capi.hip:%d)", who, __LINE__);
     const size_t need = sahs_lpips_distance_workspace_bytes(jobs, B, hw);
     if (workspace_bytes < need)
         return fail(1, "%s: workspace of %zu bytes, needs %zu (sahs_lpips_distance_workspace_bytes) (capi.hip:%d)", who, workspace_bytes, need,
                     __LINE__);
-    int e = sahs_lpips_distance_launch(jobs, features, weights, C, hw, B, out, static_cast<double *>(workspace), (hipStream_t)stream);
+    const float *second[SAHS_LPIPS_MAX_JOBS];      // rows [B, 2B) of each tensor
+    for (int k = 0; k < jobs; ++k) second[k] = features[k] + B * C[k] * hw[k];
+    int e = sahs_lpips_head_forward_launch(jobs, features, second, weights, C, hw, B, out, nullptr, static_cast<double *>(workspace),
+                                           (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
+int sahs_lpips_head_forward(int jobs, const float *const *fa, const float *const *fb, const float *const *weights, const int *C, const long *hw,
+                            long B, double *out, double *stats, size_t stats_bytes, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "sahs_lpips_head_forward";
+    bool empty;
+    if (int code = lpips_head_tables(who, jobs, fa, "fa", fb, "fb", weights, C, hw, B, &empty)) return code;
+    if (empty) return 0;
+    if (!out || !workspace) return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !out ? "out" : "workspace", __LINE__);
+    if (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(stats)) & 7u) != 0)
+        return fail(1, "%s: out, stats and workspace must be 8-byte aligned (capi.hip:%d)", who, __LINE__);
+    const size_t need = sahs_lpips_distance_workspace_bytes(jobs, B, hw), need_stats = sahs_lpips_head_stats_bytes(jobs, B, hw);
+    if (workspace_bytes < need)
+        return fail(1, "%s: workspace of %zu bytes, needs %zu (sahs_lpips_distance_workspace_bytes) (capi.hip:%d)", who, workspace_bytes, need,
+                    __LINE__);
+    if (stats && stats_bytes < need_stats)
+        return fail(1, "%s: stats of %zu bytes, needs %zu (sahs_lpips_head_stats_bytes) (capi.hip:%d)", who, stats_bytes, need_stats, __LINE__);
+    int e = sahs_lpips_head_forward_launch(jobs, fa, fb, weights, C, hw, B, out, stats, static_cast<double *>(workspace), (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
+
+int sahs_lpips_head_backward(int jobs, const float *const *fa, const float *const *fb, const float *const *weights, const int *C, const long *hw,
+                             long B, const void *g, int g_is_double, const double *stats, size_t stats_bytes, float *const *grad_a, void *stream)
+{
+    const char *who = "sahs_lpips_head_backward";
+    bool empty;
+    if (int code = lpips_head_tables(who, jobs, fa, "fa", fb, "fb", weights, C, hw, B, &empty)) return code;
+    if (empty) return 0;
+    if (!g || !stats || !grad_a) return fail(1, "%s: null pointer for %s (capi.hip:%d)", who, !g ? "g" : !stats ? "stats" : "grad_a", __LINE__);
+    for (int k = 0; k < jobs; ++k) {
+        if (!grad_a[k]) return fail(1, "%s: null pointer grad_a[%d] (capi.hip:%d)", who, k, __LINE__);
+        if ((reinterpret_cast<uintptr_t>(grad_a[k]) & 3u) != 0)
+            return fail(1, "%s: grad_a[%d] must be aligned to its 4-byte elements (capi.hip:%d)", who, k, __LINE__);
+    }
+    if ((reinterpret_cast<uintptr_t>(stats) & 7u) != 0 || (reinterpret_cast<uintptr_t>(g) & (g_is_double ? 7u : 3u)) != 0)
+        return fail(1, "%s: stats must be 8-byte aligned and g aligned to its %d-byte elements (capi.hip:%d)", who, g_is_double ? 8 : 4, __LINE__);
+    const size_t need_stats = sahs_lpips_head_stats_bytes(jobs, B, hw);
+    if (stats_bytes < need_stats)
+        return fail(1, "%s: stats of %zu bytes, needs %zu (sahs_lpips_head_stats_bytes) (capi.hip:%d)", who, stats_bytes, need_stats, __LINE__);
+    int e = sahs_lpips_head_backward_launch(jobs, fa, fb, weights, C, hw, B, g, g_is_double != 0, stats, grad_a, (hipStream_t)stream);
     return e ? hip_fail(who, e) : 0;
 }
 

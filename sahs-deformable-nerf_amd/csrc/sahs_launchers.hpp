@@ -77,11 +77,18 @@ int sahs_image_loss_launch(const float *pred, const float *target, long B, int H
                            const long *stride_target, double w_l2, double w_l1, double w_ssim, int clamp, double ssim_data_range,
                            float *grad, const long *stride_grad, double *out, double *records, hipStream_t stream);
 // lpips.hip (arguments already validated: capi.hip; records: B * sahs_lpips_distance_tiles(jobs, hw) doubles)
-int sahs_lpips_prepare_launch(const void *a, const void *b, int is_float, long B, int H, int W, const long *stride_a, const long *stride_b,
-                              int normalize, float *out, hipStream_t stream);
+// stats: null, or 3 * B * sahs_lpips_head_pixels(jobs, hw) doubles; grad_a[l]: fa[l]'s shape; clamp applies to a alone
+int sahs_lpips_prepare_launch(const void *a, const void *b, int a_is_float, int b_is_float, long B, int H, int W, const long *stride_a,
+                              const long *stride_b, int normalize, int clamp, float *out, hipStream_t stream);
+int sahs_lpips_prepare_grad_launch(const float *pred, const float *gx, long B, int H, int W, const long *stride_pred, int normalize, int clamp,
+                                   float *grad, const long *stride_grad, hipStream_t stream);
 long sahs_lpips_distance_tiles(int jobs, const long *hw);
-int sahs_lpips_distance_launch(int jobs, const float *const *features, const float *const *weights, const int *C, const long *hw, long B,
-                               double *out, double *records, hipStream_t stream);
+long sahs_lpips_head_pixels(int jobs, const long *hw);
+int sahs_lpips_head_forward_launch(int jobs, const float *const *fa, const float *const *fb, const float *const *weights, const int *C,
+                                   const long *hw, long B, double *out, double *stats, double *records, hipStream_t stream);
+int sahs_lpips_head_backward_launch(int jobs, const float *const *fa, const float *const *fb, const float *const *weights, const int *C,
+                                    const long *hw, long B, const void *g, int g_is_double, const double *stats, float *const *grad_a,
+                                    hipStream_t stream);
 // frame_products.hip (arguments already validated: capi.hip; records: B * sahs_frame_products_tiles(H, W) * 16 bytes, with disparity)
 long sahs_frame_products_tiles(int H, int W);
 int sahs_frame_products_launch(const float *rgb, int C, const long *stride_rgb, const float *disp, const float *w_bg, const float *intrinsics,

@@ -187,6 +187,38 @@ class LPIPS(object):
         finally:
             torch.backends.cudnn.deterministic = before
 
+    def loss(self, pred, target, clamp=True, channels_last=False, return_rows=False):
+        """LPIPS as a training term -> a 0-d float32 tensor, the mean over the batch, differentiable with respect to ``pred`` only.
+        pred: float32 GPU tensor (3, H, W) or (B, 3, H, W) (channels_last=True: (H, W, 3) or (B, H, W, 3)), a generator's output;
+        target: the same shape, uint8 or float32, and no gradient.  clamp=True scores pred.clamp(0, 1), as the metric scores the frame.
+        The steps: ops.lpips_prepare_loss (one launch, the clamp inside); alexnet_features of pred's B images with autograd on and of
+        target's B images under no_grad -- two calls, so that the convolution backward runs over B images and not 2B; the convolution
+        weights are plain tensors, so no weight gradients are formed --; ops.lpips_head (two launches, and one launch backward).
+        Both feature calls run in the vendor library's deterministic mode and outside autocast, as ``features`` does.  The convolution
+        BACKWARD runs later, inside the caller's backward(), under whatever mode the caller has set then: bit-reproducibility is
+        promised for the two fused ends, and for the whole gradient only if the caller sets the deterministic mode around backward().
+        A feature pixel that ReLU left all zero has a finite gradient here (autograd of the published formula gives NaN there).
+        return_rows=True: (loss, rows), rows the detached float64 (B, 6) [LPIPS, d_0 .. d_4] of ``layers``."""
+        if not torch.cuda.is_available():
+            raise _lib.SahsError("LPIPS: the loss needs a GPU (the HIP path has no CPU fallback)")
+        x_pred, x_target = ops.lpips_prepare_loss(pred, target, clamp, self.normalize, channels_last)
+        want = None if self.device is None else torch.device(self.device)
+        if want is not None and (want.type != x_pred.device.type or want.index not in (None, x_pred.device.index)):
+            raise _lib.SahsError("LPIPS: built for %s, the images live on %s" % (torch.device(self.device), x_pred.device))
+        convs, lins = self.device_weights(x_pred.device)
+        before = torch.backends.cudnn.deterministic
+        torch.backends.cudnn.deterministic = True
+        try:
+            with torch.autocast("cuda", enabled=False):
+                fa = alexnet_features(x_pred, convs)
+                with torch.no_grad():
+                    fb = alexnet_features(x_target, convs)
+        finally:
+            torch.backends.cudnn.deterministic = before
+        per_image, rows = ops.lpips_head(fa, fb, lins)
+        loss = per_image.mean()
+        return (loss, rows) if return_rows else loss
+
     def layers(self, a, b, channels_last=True):
         """-> float64 device tensor (6,) for one pair, (B, 6) for a batch: [LPIPS, d_0 .. d_4].  a, b as ops.lpips_prepare takes them."""
         if not torch.cuda.is_available():

@@ -716,6 +716,164 @@ def lpips_distance(features, lin_weights):
     return out
 
 
+def _lpips_prepare_loss_forward(pred, target, clamp, normalize):
+    """pred, target: (B, H, W, 3) views -> the one (2B, 3, H, W) buffer of sahs_lpips_prepare_loss."""
+    B, H, W, C = pred.shape
+    out = torch.empty(2 * B, 3, H, W, dtype=torch.float32, device=pred.device)
+    strides = [(ctypes.c_long * 4)(*t.stride()) for t in (pred, target)]
+    check(_lib.lib().sahs_lpips_prepare_loss(_p(pred), _p(target), _IMAGE_DTYPES[target.dtype], B, H, W, C, strides[0], strides[1],
+                                             int(bool(normalize)), int(bool(clamp)), _p(out), _stream()), "sahs_lpips_prepare_loss")
+    return out
+
+
+class LpipsPrepareLossFn(torch.autograd.Function):
+    """lpips_prepare_loss as ONE differentiable node: one launch forward, one launch backward (sahs_lpips_prepare_grad: the clamp's mask is
+    read from the saved pred).  pred, target: (B, H, W, 3) views.  -> (x_pred, x_target); x_target carries no gradient.  Not twice
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, pred, target, clamp, normalize):
+        out = _lpips_prepare_loss_forward(pred.detach(), target, clamp, normalize)
+        _save_named(ctx, pred=pred.detach())
+        ctx.clamp, ctx.normalize = bool(clamp), bool(normalize)
+        B = pred.shape[0]
+        x_pred, x_target = out[:B], out[B:]
+        ctx.mark_non_differentiable(x_target)
+        return x_pred, x_target
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gx, _g_target):
+        pred = _load_named(ctx).pred
+        B, H, W, C = pred.shape
+        gx = gx.contiguous().float()
+        grad = torch.empty_like(pred)      # (pred's strides where they are dense, so the permuted view of an NCHW tensor is written NCHW)
+        strides = [(ctypes.c_long * 4)(*t.stride()) for t in (pred, grad)]
+        check(_lib.lib().sahs_lpips_prepare_grad(_p(pred), _p(gx), B, H, W, C, strides[0], int(ctx.normalize), int(ctx.clamp), _p(grad),
+                                                 strides[1], _stream()), "sahs_lpips_prepare_grad")
+        return grad, None, None, None
+
+
+def lpips_prepare_loss(pred, target, clamp=True, normalize=False, channels_last=False):
+    """LPIPS's input stage for a training term, one launch each way (include/sahs_nerf.h: sahs_lpips_prepare_loss,
+    sahs_lpips_prepare_grad).  pred: float32 GPU tensor (3, H, W) or (B, 3, H, W) -- with channels_last=True (H, W, 3) or (B, H, W, 3) --
+    H, W >= 31; target: the same shape, torch.uint8 (taken as x / 255) or torch.float32.  Both are read in place through their strides.
+    clamp=True applies clamp(0, 1) to pred alone, then as lpips_prepare: the optional 2x - 1 and (x - shift) / scale.
+    -> (x_pred, x_target), two contiguous (B, 3, H, W) float32 views of ONE buffer, so that torch.cat is never needed.  The gradient
+    flows to ``pred`` only (it has pred's shape, and pred's layout where that is dense), through the clamp where 0 <= pred <= 1;
+    ``target`` must not require one.  Runs outside autocast."""
+    for t, name in ((pred, "pred"), (target, "target")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.SahsError("lpips_prepare_loss: %s must be a GPU tensor (the HIP path has no CPU fallback)" % name)
+        if t.device.index != torch.cuda.current_device():
+            raise _lib.SahsError("lpips_prepare_loss: %s lives on %s but the current device is cuda:%d" % (name, t.device, torch.cuda.current_device()))
+    if pred.dtype != torch.float32 or target.dtype not in _IMAGE_DTYPES:
+        raise _lib.SahsError("lpips_prepare_loss: pred must be torch.float32 and target torch.uint8 or torch.float32, got %s and %s "
+                             "(under autocast: pred.float())" % (pred.dtype, target.dtype))
+    if target.requires_grad:
+        raise _lib.SahsError("lpips_prepare_loss: target requires a gradient, and the gradient is formed for pred only (pass target.detach())")
+    if pred.shape != target.shape or pred.dim() not in (3, 4):
+        raise _lib.SahsError("lpips_prepare_loss: pred and target must have one shape, (3, H, W) or (B, 3, H, W) (channels_last=True: "
+                             "(H, W, 3) or (B, H, W, 3)), got %s and %s" % (tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() == 3:
+        pred, target = pred[None], target[None]
+    if not channels_last:
+        pred, target = pred.permute(0, 2, 3, 1), target.permute(0, 2, 3, 1)      # views: the kernel reads through the strides
+    B = pred.shape[0]
+    with torch.autocast("cuda", enabled=False):
+        if torch.is_grad_enabled() and pred.requires_grad:
+            return LpipsPrepareLossFn.apply(pred, target, bool(clamp), bool(normalize))
+        out = _lpips_prepare_loss_forward(pred.detach(), target, clamp, normalize)
+        return out[:B], out[B:]
+
+
+def _lpips_head_tables(fa, fb, lin_weights):
+    n = len(fa)
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
+    return (n, ptrs(fa), ptrs(fb), ptrs(lin_weights), (ctypes.c_int * n)(*[f.shape[1] for f in fa]),
+            (ctypes.c_long * n)(*[f.shape[2] * f.shape[3] for f in fa]), fa[0].shape[0])
+
+
+def _lpips_head_forward(fa, fb, lin_weights, want_stats):
+    """-> (rows (B, 6) float64, stats or None): sahs_lpips_head_forward."""
+    n, pa, pb, pw, Cs, hw, B = _lpips_head_tables(fa, fb, lin_weights)
+    L = _lib.lib()
+    dev = fa[0].device
+    out = torch.empty(B, 1 + LPIPS_MAX_JOBS, dtype=torch.float64, device=dev)
+    need = int(L.sahs_lpips_distance_workspace_bytes(n, B, hw))
+    work = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=dev)
+    need_stats = int(L.sahs_lpips_head_stats_bytes(n, B, hw)) if want_stats else 0
+    stats = torch.empty(max(need_stats, 8) // 8, dtype=torch.float64, device=dev) if want_stats else None
+    check(L.sahs_lpips_head_forward(n, pa, pb, pw, Cs, hw, B, _p(out), _p(stats), need_stats, _p(work), need, _stream()), "sahs_lpips_head_forward")
+    return out, stats
+
+
+class LpipsHeadFn(torch.autograd.Function):
+    """lpips_head as ONE differentiable node: the forward's two launches also store three doubles per pixel (1 / na, 1 / nb, q), and the
+    backward is one launch over all layers (include/sahs_nerf.h: sahs_lpips_head_backward).  apply(fb, lin_weights, *fa) ->
+    (per_image, rows); rows carries no gradient.  Saved: the features themselves, the weights and the statistics -- no normalised copies.
+    Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, fb, lin_weights, *fa):
+        fa = [f.detach() for f in fa]
+        rows, stats = _lpips_head_forward(fa, fb, lin_weights, True)
+        ctx.layers = len(fa)
+        _save_named(ctx, stats=stats, **{"fa%d" % l: f for l, f in enumerate(fa)}, **{"fb%d" % l: f for l, f in enumerate(fb)},
+                    **{"w%d" % l: w for l, w in enumerate(lin_weights)})
+        ctx.mark_non_differentiable(rows)
+        return rows[:, 0].float(), rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_rows):
+        s = _load_named(ctx)
+        fa, fb, ws = ([getattr(s, "%s%d" % (k, l)) for l in range(ctx.layers)] for k in ("fa", "fb", "w"))
+        n, pa, pb, pw, Cs, hw, B = _lpips_head_tables(fa, fb, ws)
+        if g.dtype != torch.float64:
+            g = g.float()
+        g = g.contiguous()
+        grads = [torch.empty_like(f) for f in fa]
+        pg = (ctypes.c_void_p * n)(*[t.data_ptr() for t in grads])
+        check(_lib.lib().sahs_lpips_head_backward(n, pa, pb, pw, Cs, hw, B, _p(g), int(g.dtype == torch.float64), _p(s.stats), s.stats.numel() * 8,
+                                                  pg, _stream()), "sahs_lpips_head_backward")
+        return (None, None) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+def lpips_head(fa, fb, lin_weights):
+    """LPIPS's head as a training term (include/sahs_nerf.h: sahs_lpips_head_forward, sahs_lpips_head_backward).  fa, fb: lists of
+    contiguous float32 GPU tensors (B, C_l, h_l, w_l), one pair per layer (1 .. 5), the features of pred and of target; lin_weights:
+    per layer its C_l channel weights, as lpips_distance takes them.
+    -> (per_image, rows): per_image (B,) float32, each image's LPIPS, differentiable with respect to ``fa`` ONLY (fb and the weights
+    get no gradient, whatever they ask for); rows the detached float64 (B, 6) [LPIPS, d_0 .. d_4] of lpips_distance, the same bits.
+    One autograd node, once differentiable: two launches forward, one backward.  A pixel whose features are all zero has a finite
+    gradient (autograd of the published formula gives NaN there); equal operands give exactly 0 and a gradient that is exactly 0.
+    Under no_grad, or when no fa[l] requires a gradient, the statistics are not stored and the result has the same bits.
+    Bit-reproducible; a batch gives the bits of its single calls.  A tensor that is not contiguous float32 is refused, not copied."""
+    fa, fb, lin_weights = list(fa), list(fb), list(lin_weights)
+    if not (len(fa) == len(fb) == len(lin_weights)) or not 1 <= len(fa) <= LPIPS_MAX_JOBS:
+        raise _lib.SahsError("lpips_head: %d fa, %d fb and %d weight tensors: needs one of each per layer and 1 .. %d layers"
+                             % (len(fa), len(fb), len(lin_weights), LPIPS_MAX_JOBS))
+    for l, (a, b, w) in enumerate(zip(fa, fb, lin_weights)):
+        for t, name in ((a, "fa[%d]" % l), (b, "fb[%d]" % l), (w, "lin_weights[%d]" % l)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise _lib.SahsError("lpips_head: %s must be a GPU tensor (the HIP path has no CPU fallback)" % name)
+            if t.device.index != torch.cuda.current_device():
+                raise _lib.SahsError("lpips_head: %s lives on %s but the current device is cuda:%d" % (name, t.device, torch.cuda.current_device()))
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.SahsError("lpips_head: %s must be contiguous float32 (features: NCHW), got %s with strides %s"
+                                     % (name, t.dtype, tuple(t.stride())))
+        if a.dim() != 4 or a.shape != b.shape or a.shape[0] != fa[0].shape[0] or w.numel() != a.shape[1]:
+            raise _lib.SahsError("lpips_head: fa[%d] is %s, fb[%d] %s, with %d weights: needs two (B, C, h, w) of one shape with the B of fa[0] "
+                                 "and C weights" % (l, tuple(a.shape), l, tuple(b.shape), w.numel()))
+    fb, lin_weights = [t.detach() for t in fb], [t.detach() for t in lin_weights]
+    with torch.autocast("cuda", enabled=False):
+        if torch.is_grad_enabled() and any(f.requires_grad for f in fa):
+            return LpipsHeadFn.apply(fb, lin_weights, *fa)
+        rows, _ = _lpips_head_forward([f.detach() for f in fa], fb, lin_weights, False)
+        return rows[:, 0].float(), rows
+
+
 def adam_step(params, grad, exp_avg, exp_avg_sq, lr, beta1=0.9, beta2=0.999, eps=1e-8, step=1, grad_scale=1.0):
     """One torch.optim.Adam update (weight_decay 0, no amsgrad) of n contiguous fp32 values, in place on params / exp_avg / exp_avg_sq, as one
     HIP launch (include/sahs_nerf.h: sahs_adam_step).  step: the 1-based count of this update; grad is read as grad * grad_scale."""

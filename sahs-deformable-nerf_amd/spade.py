@@ -293,16 +293,27 @@ class RefineLoss:
     what a refiner is scored on (metrics.score_frames: L1, PSNR, SSIM) -- as ONE fused, differentiable op with the clamp inside
     (ops.image_loss: two launches forward, one scaling backward, bit-reproducible).  ``RefineLoss()`` is the reference's objective,
     ``RefineLoss(1, 1)`` the l2 + l1 variant its audio loop keeps commented (train_get_texture_photo_audio.py:189-191).  Under
-    autocast the generator's bf16 output is widened first; the op itself runs in fp32 outside autocast."""
+    autocast the generator's bf16 output is widened first; the op itself runs in fp32 outside autocast.
+    ``lpips > 0`` adds ``lpips * lpips_model.loss(fake, target, clamp=True)``, the fourth figure frames are scored on, with
+    ``lpips_model`` a ``metrics.LPIPS`` object built from the user's weight files (metrics.LPIPS.loss: fused ends, the vendor
+    library's convolutions between them); asking for it without a model is a ValueError.  With ``lpips == 0`` nothing changes."""
 
-    def __init__(self, l2=1.0, l1=0.0, ssim=0.0, ssim_data_range=1.0):
+    def __init__(self, l2=1.0, l1=0.0, ssim=0.0, ssim_data_range=1.0, lpips=0.0, lpips_model=None):
         self.l2, self.l1, self.ssim, self.ssim_data_range = float(l2), float(l1), float(ssim), float(ssim_data_range)
+        self.lpips, self.lpips_model = float(lpips), lpips_model
+        if self.lpips > 0.0 and lpips_model is None:
+            raise ValueError("RefineLoss: lpips = %g needs lpips_model, a metrics.LPIPS object (its weights do not ship here)" % self.lpips)
 
     def __call__(self, fake, target):
-        return ops.image_loss(fake.float(), target, l2=self.l2, l1=self.l1, ssim=self.ssim, clamp=True, ssim_data_range=self.ssim_data_range)
+        fake = fake.float()
+        loss = ops.image_loss(fake, target, l2=self.l2, l1=self.l1, ssim=self.ssim, clamp=True, ssim_data_range=self.ssim_data_range)
+        if self.lpips > 0.0:
+            loss = loss + self.lpips * self.lpips_model.loss(fake, target, clamp=True)
+        return loss
 
     def __repr__(self):
-        return "RefineLoss(l2=%g, l1=%g, ssim=%g, ssim_data_range=%g)" % (self.l2, self.l1, self.ssim, self.ssim_data_range)
+        text = "RefineLoss(l2=%g, l1=%g, ssim=%g, ssim_data_range=%g" % (self.l2, self.l1, self.ssim, self.ssim_data_range)
+        return text + (", lpips=%g)" % self.lpips if self.lpips > 0.0 else ")")
 
 
 def refine_step(G, optimizer, I_src, I_raw, target, driving=None, loss=None, autocast_dtype=None):
