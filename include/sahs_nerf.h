@@ -397,6 +397,31 @@ int sahs_spade_modulate_backward_bf16(long planes, long hw, const unsigned short
                                       const float *stats, const unsigned short *grad_out, float eps, float slope, unsigned short *dx,
                                       unsigned short *dgamma, unsigned short *dbeta, float *work, void *stream);
 
+/* ---- Stage-II inference: the modulation with gamma / beta frozen (sahs-deformable-nerf_amd/spade.py: freeze_identity) ----
+ *   out[b,c,i,j] = lrelu_slope( (X[b,c,i,j] - mean[b,c]) * rstd[b,c] * (1 + gamma[g,c,i,j]) + beta[g,c,i,j] )
+ * x is (batch, channels, h, w), out (batch, channels, H, W), gamma and beta (map_batch, channels, H, W), all contiguous NCHW.
+ * map_batch == 1: ONE map shared by every frame of the batch (g = 0; it is what a frozen identity photo yields), loaded once per
+ * (channel, position) and applied to all `batch` frames -- fp32 traffic per element 4 (statistics) + 8 + 8 / batch, where the
+ * per-frame call moves 20.  map_batch == batch: g = b.  Any other map_batch is an invalid argument.
+ * up == 0: X = x, (H, W) = (h, w).  up == 1: X[b,c,i,j] = x[b,c,i>>1,j>>1], (H, W) = (2h, 2w) -- the layer applied to the nearest-
+ * neighbour 2x upsample of x, which is never formed: mean and rstd are the statistics of the SOURCE plane (every source value occurs
+ * exactly four times in X, so mean and biased variance are the same), read over h * w elements.
+ * The statistics passes and the per-element arithmetic are sahs_spade_modulate's own, so for up == 0 the output is bit for bit that
+ * call's (with the shared map repeated), and for up == 1 each phase out[:, :, di::2, dj::2] is bit for bit that call's on x with the
+ * phase of gamma and beta.  Inference only: there is no backward.  stats: sahs_spade_modulate_frozen_workspace_words(batch, channels)
+ * floats.  The channel is one gridDim.y slot and the batch is a loop inside the kernel: channels <= 65535 (more is an invalid argument
+ * whose message names the limit); batch * channels is NOT limited.  Access width: 16 bytes per operand and thread where the output
+ * row (up == 1; the plane for up == 0) divides into groups of 4 floats and every pointer is 16-byte aligned -- with up == 1 the source
+ * is read 8 bytes at a time and needs 8-byte alignment; element by element otherwise.  Three launches (more statistics launches
+ * beyond 65535 planes), no atomics, bit-reproducible.
+ * The _bf16 entry: x, gamma, beta, out are bf16 bit patterns, groups of 8; arithmetic, statistics and workspace stay fp32. */
+long sahs_spade_modulate_frozen_workspace_words(long batch, long channels);
+int sahs_spade_modulate_frozen(long batch, long channels, long h, long w, long map_batch, int up, const float *x, const float *gamma,
+                               const float *beta, float eps, float slope, float *out, float *stats, void *stream);
+int sahs_spade_modulate_frozen_bf16(long batch, long channels, long h, long w, long map_batch, int up, const unsigned short *x,
+                                    const unsigned short *gamma, const unsigned short *beta, float eps, float slope, unsigned short *out,
+                                    float *stats, void *stream);
+
 /* ---- Stage-II refiner training: spectral norm of a table of weights, fused ----
  * torch.nn.utils.spectral_norm's SpectralNorm.compute_weight (dim 0, n_power_iterations 1) for up to SAHS_SPECTRAL_NORM_MAX_JOBS weights
  * of mixed shapes per call.  Job k is a weight viewed as a contiguous row-major h[k] x w[k] fp32 matrix W (h = out channels,

@@ -81,6 +81,9 @@ SIGNATURES = {
     "sahs_spade_modulate_backward": (_I, [_L, _L, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "sahs_spade_modulate_bf16": (_I, [_L, _L, _P, _P, _P, _F, _F, _P, _P, _P]),
     "sahs_spade_modulate_backward_bf16": (_I, [_L, _L, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "sahs_spade_modulate_frozen_workspace_words": (_L, [_L, _L]),
+    "sahs_spade_modulate_frozen": (_I, [_L, _L, _L, _L, _L, _I, _P, _P, _P, _F, _F, _P, _P, _P]),
+    "sahs_spade_modulate_frozen_bf16": (_I, [_L, _L, _L, _L, _L, _I, _P, _P, _P, _F, _F, _P, _P, _P]),
     "sahs_spectral_norm_forward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "sahs_spectral_norm_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "sahs_image_metrics_workspace_bytes": (ctypes.c_size_t, [_L, _I, _I, _I]),

@@ -34,6 +34,7 @@ NO_SCRATCH = {"gemm_dma_kernel": 0, "_ZN4sahs24field_forward_f32_kernelILb0E": 0
               "field_forward_f32_kernelILb0ELi6E": 0, "field_forward_f32_kernelILb0ELi7E": 0,      # the fused sparse instances, every model
               "gemm_tn_jobs_f32_kernel": 0, "gemm_tn_jobs256_f32_kernel": 0, "adam_step_kernel": 0,      # (a streaming kernel: nothing to spill)
               "instance_stats_kernel": 0, "spade_modulate_kernel": 0, "spade_backward_sums_kernel": 0, "spade_backward_apply_kernel": 0,
+              "spade_modulate_frozen_kernel": 0, "spade_modulate_frozen_up_kernel": 0,
               # (streaming too; every instance, float and bf16 -- there eight widened values per operand live in registers)
               "spectral_norm_vectors_kernel": 0, "spectral_norm_scale_kernel": 0, "spectral_norm_backward_kernel": 0,      # (1024-thread workgroups: 128 registers)
               "field_backward_chain_rad_f32_kernel": 0, "field_backward_chain_def_f32_kernel": 0,

@@ -303,7 +303,36 @@ static int spade_backward(const char *who, int bf16, long planes, long hw, const
                                                 work, bf16, (hipStream_t)stream);
     return e ? hip_fail(who, e) : 0;
 }
+static int spade_frozen(const char *who, int bf16, long batch, long channels, long h, long w, long map_batch, int up, const void *x,
+                        const void *gamma, const void *beta, float eps, float slope, void *out, float *stats, void *stream)
+{
+    if (batch == 0 || channels == 0 || h == 0 || w == 0) return 0;
+    SPADE_REQUIRE(batch > 0 && channels > 0 && h > 0 && w > 0 && x && gamma && beta && out && stats && eps > 0.0f, "");
+    SPADE_REQUIRE(up == 0 || up == 1, "(up is 0 or 1)");
+    SPADE_REQUIRE(map_batch == 1 || map_batch == batch, "(gamma and beta have a batch of 1, shared by every frame, or of `batch`)");
+    SPADE_REQUIRE(channels <= 65535, "(channels <= 65535: one channel per gridDim.y; the batch is not limited)");
+    int e = sahs_spade_modulate_frozen_launch(batch, channels, map_batch == 1, h, w, up, x, gamma, beta, eps, slope, out, stats, bf16,
+                                              (hipStream_t)stream);
+    return e ? hip_fail(who, e) : 0;
+}
 #undef SPADE_REQUIRE
+
+long sahs_spade_modulate_frozen_workspace_words(long batch, long channels)
+{
+    return batch > 0 && channels > 0 ? sahs_spade_stats_words(batch * channels) : 0;
+}
+int sahs_spade_modulate_frozen(long batch, long channels, long h, long w, long map_batch, int up, const float *x, const float *gamma,
+                               const float *beta, float eps, float slope, float *out, float *stats, void *stream)
+{
+    return spade_frozen("sahs_spade_modulate_frozen", 0, batch, channels, h, w, map_batch, up, x, gamma, beta, eps, slope, out, stats, stream);
+}
+int sahs_spade_modulate_frozen_bf16(long batch, long channels, long h, long w, long map_batch, int up, const unsigned short *x,
+                                    const unsigned short *gamma, const unsigned short *beta, float eps, float slope, unsigned short *out,
+                                    float *stats, void *stream)
+{
+    return spade_frozen("sahs_spade_modulate_frozen_bf16", 1, batch, channels, h, w, map_batch, up, x, gamma, beta, eps, slope, out, stats,
+                        stream);
+}
 
 int sahs_spade_modulate(long planes, long hw, const float *x, const float *gamma, const float *beta, float eps, float slope, float *out,
                         float *stats, void *stream)

@@ -61,6 +61,9 @@ int sahs_spade_modulate_launch(long planes, long hw, const void *x, const void *
 int sahs_spade_modulate_backward_launch(long planes, long hw, const void *x, const void *gamma, const void *out, const float *stats,
                                         const void *grad, float eps, float slope, void *dx, void *dgamma, void *dbeta, float *work, int bf16,
                                         hipStream_t stream);
+// (x: (batch, channels, h, w); gamma, beta: a batch of 1 with shared set, of `batch` otherwise; with up they and out are (2h, 2w) planes)
+int sahs_spade_modulate_frozen_launch(long batch, long channels, int shared, long h, long w, int up, const void *x, const void *gamma,
+                                      const void *beta, float eps, float slope, void *out, float *stats, int bf16, hipStream_t stream);
 // spectral_norm.hip (the tables as host arrays of device pointers, already validated: capi.hip)
 int sahs_spectral_norm_forward_launch(int jobs, const float *const *W, float *const *u, float *const *v, void *const *out,
                                       float *const *saved, const int *h, const int *w, int out_bf16, int power_iteration, float eps,

@@ -83,6 +83,13 @@ __global__ void __launch_bounds__(256) instance_stats_kernel(long hw, const T *_
     if (threadIdx.x == 0) pp[2 * blockIdx.x + pass] = s;
 }
 
+// one element of the modulation, the same instructions in every kernel that modulates (the build forbids contraction)
+__device__ __forceinline__ float spade_element(float x, float mean, float rstd, float gamma, float beta, float slope)
+{
+    const float v = ((x - mean) * rstd) * (1.0f + gamma) + beta;
+    return v > 0.0f ? v : v * slope;
+}
+
 // the fused modulate pass: 2-D grid (chunk of the plane, plane) -- the plane index is blockIdx.y, no per-element divide -- and one group
 // per operand and thread: fp32 12 B read + 4 B written per element (the statistics pass reads 4 B more)
 template <typename T, int W>
@@ -99,11 +106,140 @@ __global__ void __launch_bounds__(256) spade_modulate_kernel(long hw, const T *_
         elem_load<W>(gamma + base, i, gv);
         elem_load<W>(beta + base, i, bv);
 #pragma unroll
-        for (int k = 0; k < W; ++k) {
-            const float v = ((xv[k] - mean) * rstd) * (1.0f + gv[k]) + bv[k];
-            o[k] = v > 0.0f ? v : v * slope;
-        }
+        for (int k = 0; k < W; ++k) o[k] = spade_element(xv[k], mean, rstd, gv[k], bv[k], slope);
         elem_store<W>(out + base, i, o);
+    }
+}
+
+// ---- the frozen modulation (Stage-II inference: gamma / beta computed once from the identity photo) ----
+// Same statistics, same element; what differs is who shares what.  The CHANNEL is on the grid and the batch is a loop in the kernel, so
+// (a) a gamma / beta map with a batch of 1 is loaded once per (channel, position) and applied to all B frames -- fp32: 12 + 8 / B bytes
+// per element where the per-frame op moves 20 -- and (b) B * C is not bounded by gridDim.y, only C is.  shared = 0: gamma / beta have the
+// batch of x and are loaded per frame (the audio-modulated blocks of Generator_audio).
+template <typename T, int W>
+__global__ void __launch_bounds__(256) spade_modulate_frozen_kernel(long B, long C, int shared, long hw, const T *__restrict__ x,
+                                                                    const T *__restrict__ gamma, const T *__restrict__ beta,
+                                                                    const float *__restrict__ stats, float eps, float slope, T *__restrict__ out)
+{
+    const long c = blockIdx.y, n = hw / W;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float gv[W], bv[W];
+        if (shared) {
+            elem_load<W>(gamma + c * hw, i, gv);
+            elem_load<W>(beta + c * hw, i, bv);
+        }
+        for (long b = 0; b < B; ++b) {
+            const long plane = b * C + c, base = plane * hw;
+            float mean, rstd, xv[W], o[W];
+            plane_norm(stats + plane * (2 * SPADE_CHUNKS), hw, eps, mean, rstd);
+            elem_load<W>(x + base, i, xv);
+            if (!shared) {
+                elem_load<W>(gamma + base, i, gv);
+                elem_load<W>(beta + base, i, bv);
+            }
+#pragma unroll
+            for (int k = 0; k < W; ++k) o[k] = spade_element(xv[k], mean, rstd, gv[k], bv[k], slope);
+            elem_store<W>(out + base, i, o);
+        }
+    }
+}
+
+// S elements of a source row: S = ELEM_VEC<T> / 2 is one 8-byte access (2 floats, 4 bf16) for an 8-byte aligned pointer, S = 1 one element
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+template <int S>
+__device__ __forceinline__ void half_load(const float *p, long g, float (&v)[S])
+{
+    if constexpr (S == 1) {
+        v[0] = p[g];
+    } else {
+        static_assert(S == 2);
+        const f32x2_t q = reinterpret_cast<const f32x2_t *>(p)[g];
+        v[0] = q[0];
+        v[1] = q[1];
+    }
+}
+template <int S>
+__device__ __forceinline__ void half_load(const unsigned short *p, long g, float (&v)[S])
+{
+    if constexpr (S == 1) {
+        v[0] = bf16_widen(p[g]);
+    } else {
+        static_assert(S == 4);
+        const u32x2_t q = reinterpret_cast<const u32x2_t *>(p)[g];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            v[2 * k] = __builtin_bit_cast(float, q[k] << 16);
+            v[2 * k + 1] = __builtin_bit_cast(float, q[k] & 0xffff0000u);
+        }
+    }
+}
+// 2 * S elements of an output row from element e on: one 16-byte group for S > 1 (e is a multiple of 2 * S there), two elements for S = 1
+template <int S, typename T>
+__device__ __forceinline__ void row_load(const T *p, long e, float (&v)[2 * S])
+{
+    if constexpr (S == 1) {
+        float t[1];
+        elem_load<1>(p, e, t);
+        v[0] = t[0];
+        elem_load<1>(p, e + 1, t);
+        v[1] = t[0];
+    } else {
+        elem_load<2 * S>(p, e / (2 * S), v);
+    }
+}
+template <int S, typename T>
+__device__ __forceinline__ void row_store(T *p, long e, const float (&v)[2 * S])
+{
+    if constexpr (S == 1) {
+        const float t0[1] = {v[0]}, t1[1] = {v[1]};
+        elem_store<1>(p, e, t0);
+        elem_store<1>(p, e + 1, t1);
+    } else {
+        elem_store<2 * S>(p, e / (2 * S), v);
+    }
+}
+
+// The same with the nearest-neighbour 2x upsample of x read in place: x is (B, C, h, w), gamma / beta / out are (.., C, 2h, 2w), and
+// X[i][j] = x[i >> 1][j >> 1] is never written anywhere.  A thread takes S source elements of row r and serves the 2 * S output elements
+// above them in rows 2r and 2r + 1.  stats are the SOURCE planes' (every source value occurs four times in X: same mean, same biased
+// variance), hw = h * w.  fp32: 1 + 8 / B (shared) + 4 bytes per OUTPUT element, and the statistics passes read a quarter of X.
+template <typename T, int S>
+__global__ void __launch_bounds__(256) spade_modulate_frozen_up_kernel(long B, long C, int shared, long h, long w, const T *__restrict__ x,
+                                                                       const T *__restrict__ gamma, const T *__restrict__ beta,
+                                                                       const float *__restrict__ stats, float eps, float slope,
+                                                                       T *__restrict__ out)
+{
+    constexpr int OW = 2 * S;
+    const long c = blockIdx.y, gw = w / S, n = h * gw, hw = h * w, ow = 2 * w, ohw = 4 * hw;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x) {
+        const long r = p / gw, e0 = 2 * r * ow + (p - r * gw) * OW, e1 = e0 + ow;      // the two output rows' first elements, in the plane
+        float g0[OW], g1[OW], b0[OW], b1[OW];
+        if (shared) {
+            row_load<S>(gamma + c * ohw, e0, g0);
+            row_load<S>(gamma + c * ohw, e1, g1);
+            row_load<S>(beta + c * ohw, e0, b0);
+            row_load<S>(beta + c * ohw, e1, b1);
+        }
+        for (long b = 0; b < B; ++b) {
+            const long plane = b * C + c, obase = plane * ohw;
+            float mean, rstd, xv[S], o0[OW], o1[OW];
+            plane_norm(stats + plane * (2 * SPADE_CHUNKS), hw, eps, mean, rstd);
+            half_load<S>(x + plane * hw, p, xv);      // (rows are whole groups: group p of the plane is group p - r * gw of row r)
+            if (!shared) {
+                row_load<S>(gamma + obase, e0, g0);
+                row_load<S>(gamma + obase, e1, g1);
+                row_load<S>(beta + obase, e0, b0);
+                row_load<S>(beta + obase, e1, b1);
+            }
+#pragma unroll
+            for (int k = 0; k < OW; ++k) {
+                o0[k] = spade_element(xv[k >> 1], mean, rstd, g0[k], b0[k], slope);
+                o1[k] = spade_element(xv[k >> 1], mean, rstd, g1[k], b1[k], slope);
+            }
+            row_store<S>(out + obase, e0, o0);
+            row_store<S>(out + obase, e1, o1);
+        }
     }
 }
 
@@ -223,6 +359,39 @@ static int spade_modulate_launch(long planes, long hw, const T *x, const T *gamm
     return (int)hipGetLastError();
 }
 
+// x: (B, C, h, w); gamma, beta: (shared ? 1 : B, C, H, W); out: (B, C, H, W); (H, W) = (h, w), or (2h, 2w) with up.  The statistics are
+// instance_stats_kernel's over the B * C source planes, 65535 (gridDim.y) planes per launch, with the group width the per-frame op
+// takes for the same x (up = 0: decided by all four pointers, as there), so mean and rstd are its bits.  Only C rides on gridDim.y.
+template <typename T>
+static int spade_frozen_launch(long B, long C, int shared, long h, long w, int up, const T *x, const T *gamma, const T *beta, float eps,
+                               float slope, T *out, float *stats, hipStream_t stream)
+{
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0) return 0;
+    if (C > 65535) return -2;      // gridDim.y (capi.hip refuses it by name first)
+    constexpr int V = ELEM_VEC<T>;
+    const long hw = h * w, planes = B * C;
+    const bool aligned8 = (reinterpret_cast<uintptr_t>(x) & 7u) == 0;
+    const bool vec = up ? (w % (V / 2) == 0 && aligned8 && spade_vec<T>(V, gamma, beta, out)) : spade_vec<T>(hw, x, gamma, beta, out);
+    const bool svec = up ? spade_vec<T>(hw, x) : vec;
+    for (long p0 = 0; p0 < planes; p0 += 65535) {
+        const dim3 sgrid(SPADE_CHUNKS, (unsigned)(planes - p0 < 65535 ? planes - p0 : 65535));
+        for (int pass = 0; pass < 2; ++pass) {
+            if (svec) instance_stats_kernel<T, V><<<sgrid, 256, 0, stream>>>(hw, x + p0 * hw, stats + p0 * (2 * SPADE_CHUNKS), pass);
+            else instance_stats_kernel<T, 1><<<sgrid, 256, 0, stream>>>(hw, x + p0 * hw, stats + p0 * (2 * SPADE_CHUNKS), pass);
+        }
+    }
+    if (up) {
+        const dim3 grid = spade_plane_grid(vec ? h * (w / (V / 2)) : hw, C);
+        if (vec) spade_modulate_frozen_up_kernel<T, V / 2><<<grid, 256, 0, stream>>>(B, C, shared, h, w, x, gamma, beta, stats, eps, slope, out);
+        else spade_modulate_frozen_up_kernel<T, 1><<<grid, 256, 0, stream>>>(B, C, shared, h, w, x, gamma, beta, stats, eps, slope, out);
+    } else {
+        const dim3 grid = spade_plane_grid(vec ? hw / V : hw, C);
+        if (vec) spade_modulate_frozen_kernel<T, V><<<grid, 256, 0, stream>>>(B, C, shared, hw, x, gamma, beta, stats, eps, slope, out);
+        else spade_modulate_frozen_kernel<T, 1><<<grid, 256, 0, stream>>>(B, C, shared, hw, x, gamma, beta, stats, eps, slope, out);
+    }
+    return (int)hipGetLastError();
+}
+
 template <typename T>
 static int spade_backward_launch(long planes, long hw, const T *x, const T *gamma, const T *out, const float *stats, const T *grad, float eps,
                                  float slope, T *dx, T *dgamma, T *dbeta, float *work, hipStream_t stream)
@@ -262,4 +431,13 @@ extern "C" int sahs_spade_modulate_backward_launch(long planes, long hw, const v
                                               (bf *)dx, (bf *)dgamma, (bf *)dbeta, work, stream)
                 : sahs::spade_backward_launch(planes, hw, (const float *)x, (const float *)gamma, (const float *)out, stats, (const float *)grad, eps,
                                               slope, (float *)dx, (float *)dgamma, (float *)dbeta, work, stream);
+}
+
+extern "C" int sahs_spade_modulate_frozen_launch(long batch, long channels, int shared, long h, long w, int up, const void *x, const void *gamma,
+                                                 const void *beta, float eps, float slope, void *out, float *stats, int bf16, hipStream_t stream)
+{
+    if (bf16) return sahs::spade_frozen_launch(batch, channels, shared, h, w, up, (const bf *)x, (const bf *)gamma, (const bf *)beta, eps, slope,
+                                               (bf *)out, stats, stream);
+    return sahs::spade_frozen_launch(batch, channels, shared, h, w, up, (const float *)x, (const float *)gamma, (const float *)beta, eps, slope,
+                                     (float *)out, stats, stream);
 }

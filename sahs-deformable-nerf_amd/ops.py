@@ -395,6 +395,39 @@ def spade_modulate(x, gamma, beta, eps=1e-5, slope=1.0):
     return _spade_modulate_forward(x, gamma, beta, eps, slope)[2]
 
 
+def spade_modulate_frozen(x, gamma, beta, eps=1e-5, slope=1.0, up=False):
+    """spade_modulate for inference with gamma / beta that do not depend on the frame (include/sahs_nerf.h: sahs_spade_modulate_frozen):
+    x (B, C, h, w); gamma, beta (Bg, C, H, W) with Bg = 1 -- one map shared by the whole batch, read once per batch -- or Bg = B;
+    up=False: (H, W) = (h, w); up=True: (H, W) = (2h, 2w) and the layer is applied to the nearest-neighbour 2x upsample of x, which is
+    never formed (statistics from the source planes).  -> (B, C, H, W).  Same statistics and arithmetic as spade_modulate, bit for bit.
+    There is NO backward: tensors that require a gradient are refused while grad mode is on (call it under torch.no_grad()).  dtype rule
+    of spade_modulate: three float32 or three bfloat16 tensors; a mixture is widened to float32; anything else is refused."""
+    dtypes = [t.dtype for t in (x, gamma, beta) if isinstance(t, torch.Tensor)]
+    if any(d not in (torch.float32, torch.bfloat16) for d in dtypes):
+        raise _lib.SahsError("spade_modulate_frozen: x, gamma, beta must be torch.float32 or torch.bfloat16, got %s" % ", ".join(str(d) for d in dtypes))
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, gamma, beta)):
+        raise _lib.SahsError("spade_modulate_frozen has no backward (inference only): a tensor requires a gradient while grad mode is on; "
+                             "call it under torch.no_grad(), or train through spade_modulate")
+    if len(set(dtypes)) > 1:
+        x, gamma, beta = (t.float() if isinstance(t, torch.Tensor) else t for t in (x, gamma, beta))
+    dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16 else torch.float32
+    x, gamma, beta = _req(x, "x", dtype), _req(gamma, "gamma", dtype), _req(beta, "beta", dtype)
+    shapes = "x %s, gamma %s, beta %s, up=%s" % (tuple(x.shape), tuple(gamma.shape), tuple(beta.shape), bool(up))
+    if x.dim() != 4 or gamma.dim() != 4 or beta.shape != gamma.shape:
+        raise _lib.SahsError("spade_modulate_frozen: x must be (B, C, h, w) and gamma, beta (1 or B, C, H, W) of one shape, got " + shapes)
+    B, C, h, w = x.shape
+    scale = 2 if up else 1
+    if tuple(gamma.shape[1:]) != (C, scale * h, scale * w) or gamma.shape[0] not in (1, B):
+        raise _lib.SahsError("spade_modulate_frozen: gamma, beta must be (1 or %d, %d, %d, %d) for this x, got %s"
+                             % (B, C, scale * h, scale * w, shapes))
+    out = torch.empty((B, C, scale * h, scale * w), dtype=dtype, device=x.device)
+    stats = torch.empty(int(_lib.lib().sahs_spade_modulate_frozen_workspace_words(B, C)), dtype=torch.float32, device=x.device)
+    name = "sahs_spade_modulate_frozen" + ("_bf16" if dtype == torch.bfloat16 else "")
+    check(getattr(_lib.lib(), name)(B, C, h, w, int(gamma.shape[0]), int(bool(up)), _p(x), _p(gamma), _p(beta), float(eps), float(slope),
+                                    _p(out), _p(stats), _stream()), name)
+    return out
+
+
 SPECTRAL_NORM_MAX_JOBS = 32      # include/sahs_nerf.h: SAHS_SPECTRAL_NORM_MAX_JOBS
 
 

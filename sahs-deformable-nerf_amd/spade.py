@@ -12,8 +12,14 @@ six elementwise passes, is ONE fused HIP kernel behind a statistics pass (``ops.
 two-launch backward in place of six autograd nodes per SPADE layer -- so the generators train: ``refine_step`` is the step of the
 reference's train_get_texture_photo.py / train_get_texture_photo_audio.py (clamp, MSE, Adam; the discriminator and the VGG loss that
 _init_spade.py also defines are never called by those loops and are not built).
+
+Inference: ``freeze_identity`` computes once what depends on the identity photo alone -- the IdEncoder, the gamma /
+beta convolutions of the SPADE layers it feeds, the eval-mode spectral-normalised weights -- and ``refine_frames`` is the loop of
+eval_get_texture_photo.py / eval_get_texture_photo_audio.py over the resulting ``FrozenRefiner``, whose modulation is
+``ops.spade_modulate_frozen`` (one gamma / beta map for a batch of frames, the nearest 2x upsamples read in place).
 """
 import contextlib
+import os
 
 import torch
 import torch.nn as nn
@@ -339,3 +345,205 @@ def refine_step(G, optimizer, I_src, I_raw, target, driving=None, loss=None, aut
     loss.backward()
     optimizer.step()
     return loss.detach()
+
+
+# ---- Stage-II inference: the generator frozen against one identity photo ----
+def _normalised_weights(G):
+    """Run every spectral-norm forward pre-hook in ``G`` once -- torch's on the submodules, or fuse_spectral_norm_'s on the module that
+    carries it -- so that each hooked convolution's ``weight`` is what eval mode normalises it to (no power iteration: G is in eval)."""
+    for m in G.modules():
+        for hook in list(m._forward_pre_hooks.values()):
+            if isinstance(hook, (SpectralNorm, _FusedSpectralNorm)):
+                hook(m, ())
+
+
+def _conv_copy(conv, dtype):
+    """(weight, bias) of a convolution as detached copies in ``dtype`` -- the cast torch.autocast makes per call, made once."""
+    return conv.weight.detach().to(dtype, copy=True), conv.bias.detach().to(dtype, copy=True)
+
+
+def _tiled_code_maps(code, channels, size, tiles=64):
+    """TiledCodeMap.nearest for a batch of codes (B, n) -> (B, channels, h, w): one map per frame, by the same index rule."""
+    h, w = int(size[0]), int(size[1])
+    cols = torch.from_numpy(TiledCodeMap._nearest_index(w, code.shape[1] * tiles) % code.shape[1]).to(code.device)
+    return code[:, cols].reshape(code.shape[0], 1, 1, w).expand(code.shape[0], channels, h, w).contiguous()
+
+
+class FrozenRefiner:
+    """What ``freeze_identity`` returns: a Stage-II generator with everything that depends on the identity photo alone computed once.
+    ``frozen(I_raw)`` / ``frozen(I_raw, driving)`` returns what ``G(I_src, I_raw[, driving])`` returns for I_raw (B, 3, H, W), running
+    per frame only the stem, each block's own and resampling convolutions, the pooling, ``ops.spade_modulate_frozen`` and ``layer8``.
+    A SNAPSHOT: it holds copies of the maps and of every weight it needs (spectral-normalised ones as eval mode normalises them), so
+    later changes to ``G`` -- an optimiser step, load_state_dict -- are not seen; freeze again after changing G.  Inference only."""
+
+    def __init__(self, size, dtype, fold_upsample, stem, blocks, layer8, audio):
+        self.size, self.dtype, self.fold_upsample = tuple(size), dtype, bool(fold_upsample)
+        self.stem, self.blocks, self.layer8, self.audio = stem, blocks, layer8, audio
+
+    def _tensors(self, maps_only=False):
+        for blk in self.blocks:
+            for key in ("spade1", "spade2", "spade_s"):
+                if blk[key][0] == "maps" or not maps_only:
+                    yield from blk[key][1]
+            if not maps_only:
+                for key in ("conv1", "conv2", "conv_s", "resample"):
+                    yield from blk[key] or ()
+        if not maps_only:
+            yield from self.stem + self.layer8
+            for conv in self.audio or ():
+                yield from conv
+
+    @property
+    def cached_map_bytes(self):
+        """Bytes of the cached gamma / beta maps alone."""
+        return sum(t.numel() * t.element_size() for t in self._tensors(maps_only=True))
+
+    @property
+    def cached_bytes(self):
+        """Bytes of everything the snapshot holds: the gamma / beta maps and the weight copies."""
+        return sum(t.numel() * t.element_size() for t in self._tensors())
+
+    @property
+    def device(self):
+        return self.layer8[0].device
+
+    def _modulate(self, layer, x, code, up=False):
+        kind, tensors = layer
+        if kind == "maps":
+            gamma, beta = tensors
+        else:      # a layer modulated by the audio code: its gamma / beta convolutions run per call, from one tiled map per code
+            size = (2 * x.shape[2], 2 * x.shape[3]) if up else x.shape[2:]
+            hidden = F.relu(F.conv2d(_tiled_code_maps(code, IdEncoder.WIDTHS[2], size), tensors[0], tensors[1], padding=1))
+            gamma, beta = F.conv2d(hidden, tensors[2], tensors[3], padding=1), F.conv2d(hidden, tensors[4], tensors[5], padding=1)
+        return ops.spade_modulate_frozen(x, gamma, beta, eps=SPADELayer.EPS, slope=SPADEBlock.SLOPE, up=up)
+
+    def __call__(self, I_raw, driving=None):
+        if I_raw.dim() != 4 or tuple(I_raw.shape[1:]) != (3,) + self.size:
+            raise ValueError("FrozenRefiner: frozen for frames of (B, 3, %d, %d), got %s (freeze_identity(..., size=...) fixes the size "
+                             "of the cached maps)" % (self.size + (tuple(I_raw.shape),)))
+        if (driving is None) != (self.audio is None):
+            raise ValueError("FrozenRefiner: a Generator_audio snapshot takes driving (16, 29) or (B, 16, 29), a Generator snapshot none")
+        with torch.no_grad():
+            code = None
+            if driving is not None:
+                if driving.shape[-2:] != (16, 29) or driving.dim() not in (2, 3) or (driving.dim() == 3 and driving.shape[0] != I_raw.shape[0]):
+                    raise ValueError("FrozenRefiner: driving must be (16, 29) or (%d, 16, 29), got %s" % (I_raw.shape[0], tuple(driving.shape)))
+                code = (driving if driving.dim() == 3 else driving.unsqueeze(0)).to(self.dtype)
+                code = code.transpose(1, 2)      # (AudioNet.forward's window 8 - 16 // 2 : 8 + 16 // 2 is all 16 rows)
+                for weight, bias in self.audio:
+                    code = F.leaky_relu(F.conv1d(code, weight, bias, stride=2, padding=1), 0.02)
+                code = code.squeeze(-1)
+            x = F.avg_pool2d(F.conv2d(I_raw.to(self.dtype), self.stem[0], self.stem[1], padding=1), 2, 2)
+            for blk in self.blocks:
+                main = F.conv2d(self._modulate(blk["spade1"], x, code), blk["conv1"][0], blk["conv1"][1], padding=1)
+                skip, fold = x, False
+                if blk["how"] == "down":
+                    main, skip = F.avg_pool2d(main, 2, 2), F.conv2d(skip, blk["resample"][0], blk["resample"][1], stride=2, padding=1)
+                if blk["how"] == "up":
+                    skip = F.conv_transpose2d(skip, blk["resample"][0], blk["resample"][1], stride=2, padding=1, output_padding=1)
+                    fold = self.fold_upsample
+                    if not fold:
+                        main = F.interpolate(main, scale_factor=2, mode="nearest")
+                main = F.conv2d(self._modulate(blk["spade2"], main, code, up=fold), blk["conv2"][0], blk["conv2"][1], padding=1)
+                x = F.conv2d(self._modulate(blk["spade_s"], skip, code), blk["conv_s"][0], blk["conv_s"][1], padding=1) + main
+            y = F.conv2d(x, self.layer8[0], self.layer8[1], padding=1)
+        return y.float() if self.dtype == torch.bfloat16 else y
+
+
+def freeze_identity(G, I_src, size=None, dtype=torch.float32, fold_upsample=True):
+    """Freeze a Generator or Generator_audio against the identity photo ``I_src`` (1, 3, H, W) -> a ``FrozenRefiner`` for frames of
+    ``size`` (H, W) (default: the photo's).  Computed ONCE here, under no_grad: the identity maps and, for every SPADE layer they feed,
+    gamma and beta at that layer's own resolution; every convolution weight of the per-frame path, spectral-normalised ones as eval
+    mode normalises them (torch's hooks or fuse_spectral_norm_'s).  For Generator that is 75 % of the forward's multiply-adds; for
+    Generator_audio the layers modulated by the audio code keep their gamma / beta convolutions per call.
+    ``G`` must be in eval mode (batch norm's batch statistics and spectral norm's power iteration would make the snapshot wrong).  The
+    result is a copy: it does not follow later changes to ``G``.
+    dtype=torch.bfloat16: maps and weights are computed as ``G`` under ``torch.autocast(device, torch.bfloat16)`` computes them and
+    stored in bf16; the per-frame path then runs on bf16 tensors with no per-call casts and returns float32.  torch.float64 is taken
+    too (with ``G.double()``: the host tests).
+    fold_upsample: the nearest 2x upsample of the three "up" blocks is read in place by the modulation (``up=True``) instead of
+    written out by F.interpolate."""
+    if dtype not in (torch.float32, torch.bfloat16, torch.float64):
+        raise ValueError("freeze_identity: dtype must be torch.float32, torch.bfloat16 or torch.float64, got %r" % (dtype,))
+    if not isinstance(G, (Generator, Generator_audio)):
+        raise ValueError("freeze_identity: G must be a Generator or a Generator_audio, got %s" % type(G).__name__)
+    if any(m.training for m in G.modules()):
+        raise ValueError("freeze_identity: G must be in eval mode (call G.eval()): batch norm's batch statistics and spectral norm's "
+                         "power iteration would make the snapshot wrong")
+    if I_src.dim() != 4 or I_src.shape[0] != 1 or I_src.shape[1] != 3:
+        raise ValueError("freeze_identity: I_src must be (1, 3, H, W), got %s" % (tuple(I_src.shape),))
+    size = tuple(int(s) for s in (I_src.shape[2:] if size is None else size))
+    audio = isinstance(G, Generator_audio)
+    autocast = torch.autocast(I_src.device.type, dtype=torch.bfloat16) if dtype == torch.bfloat16 else contextlib.nullcontext()
+    net = G.refine_network
+    with torch.no_grad(), autocast:
+        _normalised_weights(G)
+        fids = G.idencoder(I_src)
+
+        def layer_state(layer, which, res):
+            if audio and which == 2:
+                return ("audio", _conv_copy(layer.mlp_shared[0], dtype) + _conv_copy(layer.conv_gamma, dtype) + _conv_copy(layer.conv_beta, dtype))
+            hidden = layer.mlp_shared(F.interpolate(fids[which], size=res, mode="nearest"))
+            return ("maps", (layer.conv_gamma(hidden).to(dtype, copy=True), layer.conv_beta(hidden).to(dtype, copy=True)))
+
+        res, blocks = (size[0] // 2, size[1] // 2), []
+        for k, (_, _, which, how) in enumerate(RefineNetwork.PLAN):
+            block = getattr(net, "layer%d" % (k + 2))
+            after = {"down": (res[0] // 2, res[1] // 2), "up": (2 * res[0], 2 * res[1]), None: res}[how]
+            resample = {"down": getattr(block, "residual_downsample", None), "up": getattr(block, "residual_upsample", None), None: None}[how]
+            blocks.append(dict(how=how, spade1=layer_state(block.spade1, which, res), spade2=layer_state(block.spade2, which, after),
+                               spade_s=layer_state(block.spade_s, which, after), conv1=_conv_copy(block.conv1_sn, dtype),
+                               conv2=_conv_copy(block.conv2_sn, dtype), conv_s=_conv_copy(block.conv_s, dtype),
+                               resample=None if resample is None else _conv_copy(resample, dtype)))
+            res = after
+        audio_convs = [_conv_copy(m, dtype) for m in G.AudioNet.encoder_conv if isinstance(m, nn.Conv1d)] if audio else None
+        return FrozenRefiner(size, dtype, fold_upsample, _conv_copy(net.layer1[0], dtype), blocks, _conv_copy(net.layer8, dtype), audio_convs)
+
+
+def _frame_bytes(frame, device, quantise):
+    """One frame of refine_frames' input -> (H, W, 3) uint8, or float as it is with quantise=False, on ``device``."""
+    frame = torch.as_tensor(frame).to(device)
+    if frame.dim() != 3 or frame.shape[2] != 3:
+        raise ValueError("refine_frames: a frame must be (H, W, 3), got %s" % (tuple(frame.shape),))
+    if frame.dtype == torch.uint8 or (not quantise and frame.is_floating_point()):
+        return frame
+    if frame.is_floating_point():
+        return (frame.clamp(0.0, 1.0) * 255).to(torch.uint8)      # evaluation.cast_to_image: what the PNG between the stages holds
+    raise ValueError("refine_frames: frames are uint8 or float (H, W, 3), got %s" % frame.dtype)
+
+
+def refine_frames(frozen, frames, driving=None, batch=8, quantise=True, savedir=None, log=print):
+    """The Stage-II evaluation loop (eval_get_texture_photo.py / eval_get_texture_photo_audio.py): every Stage-I frame through the frozen
+    generator, clipped, x255, truncated to bytes -> the list of (H, W, 3) uint8 tensors on the frozen model's device, also written as
+    ``f_%04d.png`` (numbered from 0) under ``savedir`` when given.
+    frames: an iterable (a generator works) of (H, W, 3) uint8 arrays or tensors, on any device -- a PNG's content, or
+    ``render_frames(..., fused_products=True)[i]["bytes"]["image"]`` -- or float (H, W, 3) tensors in [0, 1]; those go through the
+    cast_to_image rule first when ``quantise`` (the reference always reads a PNG), and are fed as they are otherwise.  Bytes become
+    the reference's input: / 255 in float32, CHW.  driving: a sequence of (16, 29) audio windows, one per frame, for a
+    Generator_audio snapshot.  Up to ``batch`` frames go through ``frozen`` per call."""
+    from .evaluation import _save_png
+    batch, out, n = max(int(batch), 1), [], 0
+    windows = None if driving is None else iter(driving)
+
+    def flush(chunk):
+        nonlocal n
+        x = torch.stack([f.to(torch.float32) / 255 if f.dtype == torch.uint8 else f.to(torch.float32) for f in chunk]).permute(0, 3, 1, 2)
+        d = None if windows is None else torch.stack([torch.as_tensor(next(windows)).to(frozen.device) for _ in chunk])
+        y = frozen(x.contiguous()) if d is None else frozen(x.contiguous(), d)
+        for img in (y.clamp(0.0, 1.0) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous():
+            if savedir is not None:
+                _save_png(os.path.join(savedir, "f_%04d.png" % n), img.cpu().numpy())
+            out.append(img)
+            n += 1
+
+    chunk = []
+    for frame in frames:
+        chunk.append(_frame_bytes(frame, frozen.device, quantise))
+        if len(chunk) == batch:
+            flush(chunk)
+            chunk = []
+    if chunk:
+        flush(chunk)
+    if log is not None:
+        log("refine_frames: %d frames%s" % (n, "" if savedir is None else " -> " + str(savedir)))
+    return out
