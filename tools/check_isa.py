@@ -3,10 +3,10 @@
 
     python tools/check_isa.py field_bwd_tn_jobs.hip gemm_dma_kernel      (the unit that is built: it includes field_bwd_gemm.hip)
     python tools/check_isa.py field_bwd_tn_jobs.hip gemm_tn_jobs
-    python tools/check_isa.py field_bf16w.hip field_forward_bf16w_kernel
+    python tools/check_isa.py field_bf16w.hip field_forward_bf16w_kernel [SAHS_MODEL: 0, 1 or 2] [defines ...]
 
-Compiles the source to gfx950 assembly with the product's flags (`build.py`), cuts out every function whose (mangled) name
-contains the pattern and prints, per function: scratch size, VGPR/AGPR counts, and how many of each memory / wait instruction it
+Compiles the unit to gfx950 assembly with the command the build uses for it (`build.py: unit_command`), prints that command, cuts out
+every function whose (mangled) name contains the pattern and prints, per function: scratch size, VGPR/AGPR counts, and how many of each memory / wait instruction it
 holds -- in total and inside its hottest loop (the back-edge span with the most MFMAs).  What it was written for: a counted
 `s_waitcnt vmcnt(N)` behind LDS-DMA is only right if NO other VMEM instruction (spill reload, hoisted load) shares the wave's
 stream; DESIGN.md section 7a records the audit of gemm_dma_kernel made with it.
@@ -37,11 +37,12 @@ def count(lines):
 def main():
     src, pat = sys.argv[1], sys.argv[2]
     b = importlib.import_module("sahs-deformable-nerf_amd.build")
-    path = os.path.join(b.CSRC, src)
-    extra = (b.FIELD_FLAGS if src.startswith("field_") else []) + b.PER_FILE_FLAGS.get(src, []) + ["-D" + d for d in sys.argv[3:]]
+    model = next((int(a) for a in sys.argv[3:] if a.isdigit()), 0)
     with tempfile.TemporaryDirectory() as tmp:
         asm = os.path.join(tmp, "k.s")
-        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + b.FLAGS + extra + ["--cuda-device-only", "-S", path, "-o", asm], check=True, stderr=subprocess.DEVNULL)
+        cmd = b.unit_command(src, model, [a for a in sys.argv[3:] if not a.isdigit()], "isa", asm)
+        print(" ".join(cmd))
+        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         text = open(asm).read()
     # functions: "name:" ... ".Lfunc_end"
     for m in re.finditer(r"^(\S*%s\S*):[^\n]*\n(.*?)^\.Lfunc_end\d+:" % re.escape(pat), text, re.S | re.M):

@@ -14,9 +14,11 @@ Hence the first wait with n <= k retires it.  (Scalar-memory loads also count in
 counted in k, which only makes the test stricter.)  The scan is over the function's instructions in textual order and gives up after
 MAX_SCAN instructions or at the function's end -- a read that is never retired is reported as such.
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++20 <flags of build.py> --cuda-device-only -S csrc/field_bf16w.hip -o /tmp/w.s
+    hipcc <the build's flags for that unit> --cuda-device-only -S csrc/field_bf16w.hip -o /tmp/w.s
+    (`tools/check_isa.py field_bf16w.hip field_forward_bf16w_kernel [model]` prints the command: build.py's unit_command)
     python tools/check_lds_inflight.py /tmp/w.s field_forward_bf16w_kernel
-build.py runs this on every build of the kernels listed in its HAND_SCHEDULED table."""
+build.py runs this on every build, once per unit and model, for the kernels its unit table marks as hand-scheduled (HAND_SCHEDULED),
+and rebuilds when this file changes."""
 import re
 import sys
 

@@ -1,6 +1,7 @@
 """Compare the kernels of two gfx950 assembly files, names aside: is the device code of B the device code of A?
 
-    hipcc <the build's flags for that source> --cuda-device-only -S csrc/x.hip -o x.s      (tools/check_isa.py prints the command)
+    hipcc <the build's flags for that unit> --cuda-device-only -S csrc/x.hip -o x.s
+    (build.py: unit_command(..., "isa", "x.s"); `tools/check_isa.py x.hip <kernel> [model]` prints the command it runs)
     python tools/compare_isa.py A.s B.s [kernel name pattern]
 
 Made for moving kernels between translation units and files (field_bwd.hip -> field_bwd_gemm.hip -> field_bwd_tn_jobs.hip, which

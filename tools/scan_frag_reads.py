@@ -8,7 +8,8 @@ other wave can cover the round trip.  This listing is what showed it (LAB_NOTES.
 1,411 of the fine pass's 2,208 reads sat directly in front of their MFMA.
 
     python tools/scan_frag_reads.py kernels.s [kernel-name-substring]
-    (kernels.s: hipcc <the build's flags for that source> --cuda-device-only -S csrc/x.hip -o kernels.s; tools/check_isa.py prints the command)
+    (kernels.s: hipcc <the build's flags for that unit> --cuda-device-only -S csrc/x.hip -o kernels.s -- build.py: unit_command;
+    `tools/check_isa.py x.hip <kernel> [model]` prints the command it runs)
 
 Per kernel: instructions, MFMAs, `ds_read_b128`, and the histogram {MFMAs issued between a read and the first MFMA that takes its
 destination as the A operand: reads}; "other" = reads first used by something else (activations, records).

@@ -7,7 +7,7 @@ a drain of the weight prefetch (f32 backward chains: 16 per sample tile until th
 
     python tools/scan_isa_stalls.py csrc/field_bwd_chain_f32.hip [kernel-name-substring] [-DSAHS_MODEL=1 ...]
 
-Compiles the source for gfx950 with the library's flags (device side only, -S) and prints per kernel: MFMAs, instructions and branches
+Compiles the unit for gfx950 with the build's command for it (`build.py: unit_command`; device side only, -S) and prints per kernel: MFMAs, instructions and branches
 between the first and the last MFMA, `vmcnt(0)` waits that are not part of a barrier (with the plain load they most likely wait for and how
 many MFMAs into the kernel body they sit)."""
 import importlib.util
@@ -24,7 +24,6 @@ PKG = os.path.join(REPO, "sahs-deformable-nerf_amd")
 def main():
     if len(sys.argv) < 2:
         raise SystemExit(__doc__)
-    src = sys.argv[1] if os.path.exists(sys.argv[1]) else os.path.join(PKG, sys.argv[1])
     pat = next((a for a in sys.argv[2:] if not a.startswith("-")), "")
     extra = [a for a in sys.argv[2:] if a.startswith("-")]
     spec = importlib.util.spec_from_file_location("sahs_build", os.path.join(PKG, "build.py"))
@@ -32,8 +31,7 @@ def main():
     spec.loader.exec_module(b)
     model = next((int(a.split("=")[1]) for a in extra if a.startswith("-DSAHS_MODEL=")), 0)
     out = os.path.join(tempfile.mkdtemp(prefix="isa_"), "k.s")
-    cmd = b._compile_cmd(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), os.path.basename(src), model, []) + \
-        [a for a in extra if not a.startswith("-DSAHS_MODEL=")] + ["--cuda-device-only", "-S", src, "-o", out]
+    cmd = b.unit_command(sys.argv[1], model, [], "isa", out) + [a for a in extra if not a.startswith("-DSAHS_MODEL=")]
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
     txt = open(out).read()
     for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)s_endpgm", txt, re.S | re.M):

@@ -8,7 +8,8 @@ of the tile's last MFMA.  A wave issues in order: a bias read directly in front 
 out the MFMA's latency.  Beside tools/scan_frag_reads.py (the A operands) this lists the other two:
 
     python tools/scan_tile_edges.py kernels.s [kernel-name-substring]
-    (kernels.s: hipcc <the build's flags for that source> --cuda-device-only -S csrc/x.hip -o kernels.s; tools/check_isa.py prints the command)
+    (kernels.s: hipcc <the build's flags for that unit> --cuda-device-only -S csrc/x.hip -o kernels.s -- build.py: unit_command;
+    `tools/check_isa.py x.hip <kernel> [model]` prints the command it runs)
 
 Per kernel, two histograms:
   tile starts   {MFMAs issued between a `ds_read_b128` and the first MFMA that takes its destination as srcC: reads}
